@@ -2,7 +2,15 @@
 """Benchmark of the MI355X render path on BASELINE.json's metric.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config B] [--traversal brute|bvh]
-                    [--no-cpu-baseline] [--no-alt] [--no-config-c] [--no-config-e] [--no-config-w] [--no-scalar]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-alt] [--no-config-c]
+                    [--no-config-e] [--no-config-w] [--no-scalar]]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, ms_per_step, the roofline of the timed launches).  --full adds
+every leg that takes runs of its own: the other traversal, the scalar-VALU
+kernel, the CPU baseline with parity, and configs C, E and W (the --no-* flags
+take single legs out of a --full run).  --dump-outputs DIR writes the image of
+the last timed step to DIR/image.npy (float32) before anything else runs.
 
 --gpus N > 1 without a launcher starts N ranks itself (torch.distributed.run,
 one process per GPU, master 127.0.0.1); under a launcher WORLD_SIZE must equal N.
@@ -24,6 +32,7 @@ Prints ONE JSON line (rank 0):
                 `traffic` = PMC-measured HBM bytes per launch from
                 profiles/pmc_config<X>.json, attached only when that profile was
                 taken of the same kernel variant built from the same kernel sources
+and with --full:
   cpu_baseline  the CPU restatement of compute.glsl (oracle/, reference-faithful
                 BVH traversal) on the host CPUs this job may use (the cgroup CPU
                 quota of a GPU box), on a bounded evenly spread pixel sample at
@@ -86,6 +95,12 @@ def parse():
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--traversal", default="brute", choices=["brute", "bvh"],
                     help="brute = the north-star kernel (default); bvh = the reference's traversal on the GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg that takes runs of its own: the other traversal, "
+                         "the scalar-VALU kernel, the CPU baseline with parity, configs C, E and W")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image of the last timed step to DIR/image.npy (float32; a fixed seeded pixel "
+                         "sample, with DIR/image_sample_index.npy, when the image exceeds 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alt", action="store_true", help="skip timing the other traversal beside the headline")
     ap.add_argument("--no-config-c", action="store_true", help="skip the config C (north-star target) leg")
@@ -98,7 +113,10 @@ def parse():
     ap.add_argument("--plumbing", action="store_true",
                     help="launch/collective path only, no GPU (CPU tests of --gpus N): each rank gathers a synthetic "
                          "slab of its image rows and rank 0 checks the assembled image")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def free_port():
@@ -465,6 +483,29 @@ def config_leg(torch, rt2, stream, threads, host, seconds, do_cpu, name="C"):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: everything written stays within this
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(folder, image):
+    """--dump-outputs: the image the timed path returned in its last step
+    (H x W x RGBA float32, what a caller of the render + resolve receives) as
+    DIR/image.npy.  An image beyond the size limit (config D: 4K) is written
+    as a fixed seeded sample of its pixels, in raster order, (n, 4), with their
+    flat pixel indices in DIR/image_sample_index.npy (float64: exact)."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    if image.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(folder, "image.npy"), image)
+        return
+    flat = image.reshape(-1, image.shape[-1])
+    n = DUMP_LIMIT_BYTES // 2 // (flat.shape[1] * 4 + 8)  # pixels + indices: half the limit
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.shape[0], size=n, replace=False))
+    np.save(os.path.join(folder, "image.npy"), flat[idx])
+    np.save(os.path.join(folder, "image_sample_index.npy"), idx.astype(np.float64))
+
+
 def main():
     args = parse()
     ensure_world(args)  # before any GPU call: may start the N ranks and exit
@@ -587,6 +628,13 @@ def main():
         "roofline": rf,
         "cpu_baseline": None,
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, img.cpu().numpy())
+    if not args.full:  # a plain run ends here: every leg below takes runs of its own
+        print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     gpu_imgs = {args.traversal: img.cpu().numpy() if img is not None else None}
     img_main = img.clone() if img is not None else None  # the headline image (renderer.image is reused below)
     gpu_values = {args.traversal: value}

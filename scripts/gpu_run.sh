@@ -10,7 +10,8 @@
 #                    e.g. AB="B:282,320:5 C:293,330:1:--width 480 --height 270 --frames 2"
 #   STATSV="<cfg>:<variants> ..."   diagnostic counters (scripts/mfma_stats.py)
 #   SHARD="<cfg>[:<variants>] ..."  every rank's slab on one GPU (scripts/shard_probe.py)
-#   BENCH="<args>"   python bench.py <args> -> gpurun_out/bench<TAG>.json ("default" = no args)
+#   BENCH="<args>"   python bench.py <args> -> bench_<TAG>.json in the output folder
+#                    ("default" = --full: the headline and every leg beside it)
 #   STATS="B C E"    rocprofv3 --kernel-trace --stats of a bench run per config
 #   PMC="B C E"      PMC passes (scripts/profile_pmc.sh) of the bench's render kernel per config
 #   TAG=<name>       suffix of the output files
@@ -50,7 +51,7 @@ for spec in ${SHARD}; do
   echo "shard probe $cfg ok"
 done
 if [ -n "${BENCH}" ]; then
-  bargs="${BENCH}"; [ "${BENCH}" = default ] && bargs=""
+  bargs="${BENCH}"; [ "${BENCH}" = default ] && bargs="--full"
   timeout -k 10 900 python bench.py ${bargs} > "gpurun_out/bench_$T.json" 2> "gpurun_out/bench_$T.err" \
     || { echo "bench failed"; tail -20 "gpurun_out/bench_$T.err"; exit 1; }
   echo "bench ok"; cut -c1-600 "gpurun_out/bench_$T.json"

@@ -134,6 +134,41 @@ def test_kernel_labels():
     assert bench.kernel_label(None) is None
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: an image within the size limit is written whole, as
+    float32; a larger one as a fixed seeded pixel sample with its indices,
+    the same from call to call and within the limit on disk."""
+    import numpy as np
+    img = np.arange(30 * 50 * 4, dtype=np.float32).reshape(30, 50, 4)
+    bench.dump_outputs(str(tmp_path / "whole"), img)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["image.npy"]
+    got = np.load(tmp_path / "whole" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), img)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["image.npy", "image_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 4096
+    px, idx = np.load(tmp_path / "a" / "image.npy"), np.load(tmp_path / "a" / "image_sample_index.npy")
+    assert px.dtype == np.float32 and idx.dtype == np.float64
+    assert len(idx) == len(px) > 0 and (np.diff(idx) > 0).all()
+    assert np.array_equal(px, img.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(px, np.load(tmp_path / "b" / "image.npy"))
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "image_sample_index.npy"))
+
+
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
 def _run_bench(args, env_extra=None, timeout=240):
     import subprocess
     env = dict(os.environ)
