@@ -7,7 +7,6 @@
 //   SmemSpec     records through the scalar data cache (product default)
 //   SplitSpec    several waves per 64 rays, each sweeping a share of the triangles
 //   TiledSpec    records streamed through LDS tiles (large scenes)
-//   ResidentSpec whole scene resident in LDS (experiment builds)
 // The assist kernel (idle waves help busy ones; multi-GPU slabs) is in
 // rt2_assist.h.  Included by rt2_render.hip only (one translation unit;
 // internal linkage).
@@ -36,36 +35,6 @@ struct TiledSpec {
     int group;
     Filter filter;
 };
-struct ResidentSpec {
-    int block;
-    int group;
-    Filter filter;
-};
-
-// RESIDENT: all triangles in LDS, waves independent after the initial load.
-template <ResidentSpec S>
-__global__ __launch_bounds__(S.block) void render_resident(RenderParams p) {
-    extern __shared__ float4 lds[];
-    const int n4 = 3 * p.n_tris;
-    for (int i = threadIdx.x; i < n4; i += S.block) lds[i] = p.tri[i];
-    __syncthreads();
-    Lane L;
-    lane_init(L);
-    for (;;) {
-        advance(L, p);
-        if (!__any(L.st == ST_TRACE)) break;
-        if (L.st == ST_TRACE) {
-            L.bounce += 1;
-            L.segs += 1;
-            float best = 1e38f, bestK = 1e38f * 1.0009765625f;
-            int bi = -1;
-            sweep_masked<S.group, false, S.filter>(L.o, L.d, lds, nullptr, p.n_tris, 0, best, bi, bestK);
-            shade(L, p, best, bi);
-        }
-    }
-    flush_counters(L, p);
-}
-
 // TILED: triangles streamed through LDS in tiles of p.tile_tris (coalesced
 // 16-B loads); the workgroup sweeps each tile in lockstep, so one tile serves
 // all S.block lanes.

@@ -74,7 +74,7 @@ struct rt2_scene {
     int plk_ok = 0;                             // sweep_plk usable: <= 1/64 of the triangles outside its range
     int plk_outside = 0;                        // triangles with an always-pass record
     float plk_A = 0.0f;                         // max |a_i| over the triangles
-    _Float16* d_mfma = nullptr;                 // render_mfma filter records (rt2_mfma.h)
+    _Float16* d_mfma = nullptr;                 // 16x16x32 filter records (the filter probe's layout 0; ensure_mfma16)
     float* d_mfma_tau = nullptr;                // per-triangle record scale
     _Float16* d_mfma_k16 = nullptr;             // sweep_k16 records (32-triangle groups, 7 KiB each)
     float* d_mfma_k16_tau = nullptr;            // per-triangle record scale (same values as d_mfma_tau)
@@ -415,8 +415,7 @@ static int scene_init(rt2_scene* s, const rt2_triangle* tris, int32_t n_tris, co
         // matrix-core filter records in the k16 layout (sweep_k16 and its
         // 5-product form): 7 KiB per 32 triangles; the prep's flags give the
         // scene's largest |a_i|, the filter's range check.  (The 16x16x32
-        // layout of the experiment variants and the probe's layout 0 is built
-        // on first use: ensure_mfma16.)
+        // layout of the probe's layout 0 is built on first use: ensure_mfma16.)
         const int n_pad32 = (n_tris + 31) / 32 * 32;
         HIPCHECK(hipMalloc(&s->d_mfma_k16, (size_t)n_pad32 * kK16Ops * 16 * sizeof(_Float16)));
         HIPCHECK(hipMalloc(&s->d_mfma_k16_tau, (size_t)n_pad32 * sizeof(float)));
@@ -444,8 +443,8 @@ static int scene_init(rt2_scene* s, const rt2_triangle* tris, int32_t n_tris, co
     return 0;
 }
 
-// The 16x16x32 record layout (5 KiB per 16 triangles: the experiment
-// variants of that form and the filter probe's layout 0), built on first use
+// The 16x16x32 record layout (5 KiB per 16 triangles: the filter probe's
+// layout 0 and rt2_scene_export), built on first use
 // so that a product scene does not keep 320 B per triangle it never reads.
 static int ensure_mfma16(rt2_scene* s) {
     if (s->d_mfma || s->n_tris <= 0) return 0;
@@ -519,7 +518,7 @@ constexpr int kTileTris = 1024;  // 48 KiB of LDS per tile
 // A/B experiments measured in DESIGN.md ("Tried and measured") are compiled
 // only with -DRT2_EXPERIMENTS (make EXPERIMENTS=1).
 enum Kind : int {
-    K_RESIDENT = 0, K_TILED = 1, K_SMEM = 2, K_SPLIT = 3, K_ASSIST = 4, K_MFMA = 9, K_MASSIST = 10,  // brute force
+    K_TILED = 1, K_SMEM = 2, K_SPLIT = 3, K_ASSIST = 4, K_MFMA = 9,  // brute force
     K_BVH = 5, K_BVH2 = 6, K_BVH3 = 7, K_BVH4 = 8                                     // BVH (kind >= K_BVH)
 };
 struct Variant {
@@ -527,8 +526,9 @@ struct Variant {
     int kind;
     int block;
     hipError_t (*launch)(const RenderParams&, int blocks, size_t lds, hipStream_t st);
-    const void* kernel;
+    void (*kernel)(RenderParams);
     const char* name;
+    int max_groups = 0;  // largest scene the kernel holds, in 32-triangle groups (0 = no limit)
 };
 
 template <auto K, int BLOCK>
@@ -536,8 +536,8 @@ hipError_t launch_k(const RenderParams& p, int blocks, size_t lds, hipStream_t s
     hipLaunchKernelGGL(K, dim3(blocks), dim3(BLOCK), lds, st, p);
     return hipGetLastError();
 }
-#define RT2_VARIANT(ID, KIND, KERNEL, BLOCK, NAME) \
-    Variant { ID, KIND, BLOCK, launch_k<KERNEL, BLOCK>, reinterpret_cast<const void*>(KERNEL), NAME }
+#define RT2_VARIANT(ID, KIND, KERNEL, BLOCK, NAME, ...) \
+    Variant { ID, KIND, BLOCK, launch_k<KERNEL, BLOCK>, KERNEL, NAME __VA_OPT__(, ) __VA_ARGS__ }
 
 // product kernels
 constexpr SmemSpec kSmemDefault{.block = 256, .group = 8, .filter = Filter::Max3, .tail = Tail::Coop,
@@ -554,115 +554,19 @@ constexpr AssistSpec assist12_x(int coop) {
 #endif
 constexpr TiledSpec kTiledLarge{.block = 512, .group = 4, .filter = Filter::Max3};
 constexpr AssistSpec kAssist12{.waves_per_block = 12, .group = 8, .filter = Filter::Max3, .waves = 6, .coop_rays = 32};
-constexpr MfmaSpec kMfmaT8Y4{.block = 256, .waves = 4, .tail_lanes = 8, .imax = true, .minred = true, .ymma = true,
-                             .tshift = 12};
-// k16 sweep (v_mfma_f32_32x32x16_f16, 8 products per 1,024 pairs)
-constexpr MfmaSpec k16_spec(int waves, bool afrag_lds = false, bool diag = false, bool rsplit = false,
-                           bool prefetch = false) {
-    return MfmaSpec{.block = 256, .waves = waves, .tail_lanes = 8, .imax = true, .prefetch = prefetch,
-                    .minred = true, .diag = diag, .ymma = true, .tshift = 12, .k16 = true, .afrag_lds = afrag_lds,
-                    .rsplit = rsplit};
+// the 5-product form, every wave reading the records from L2 (rt2_mfma.h render_mfma)
+constexpr MfmaSpec kMfmaK5{.block = 256, .waves = 3, .tail_lanes = 8};
+// records resident in LDS (rt2_k5_resident.h): one 16-wave workgroup per CU, the lean lane state; l2 = the L2
+// continuation (39..256 groups), fair = fair-share issue priority (rank slabs), lane_w = each ray's own W in the bound
+constexpr MfmaSpec kt_res(bool l2, bool fair, bool lane_w, int phase_prio = 0, bool diag = false) {
+    return MfmaSpec{.block = 1024, .waves = 4, .tail_lanes = 4, .diag = diag, .fair_prio = fair,
+                    .phase_prio = phase_prio, .kt_lane_w = lane_w, .lean = true, .res_l2 = l2};
 }
-constexpr MfmaSpec kMfmaK16 = [] {
-    MfmaSpec x = k16_spec(3);
-    x.lane_lds = true;
-    x.serial = 4;
-    x.compact = true;
-    return x;
-}();
-constexpr MfmaSpec kMfmaK16W4 = [] {
-    MfmaSpec x = kMfmaK16;
-    x.waves = 4;
-    x.lane_lds = 2;
-    return x;
-}();
-constexpr MfmaSpec kMfmaK5 = [] {
-    MfmaSpec x = kMfmaK16;
-    x.k5 = true;
-    return x;
-}();
-constexpr MfmaSpec kMfmaK5W4 = [] {
-    MfmaSpec x = kMfmaK16W4;
-    x.k5 = true;
-    return x;
-}();
-constexpr MfmaSpec kMfmaK5NoTn = [] {
-    MfmaSpec x = kMfmaK5;
-    x.no_tn = true;
-    return x;
-}();
-constexpr MfmaSpec kMfmaK5NoTnW4 = [] {
-    MfmaSpec x = kMfmaK5W4;
-    x.no_tn = true;
-    return x;
-}();
-// the small-scene kernel (233) with the cooperative drain at <= 4 live rays
-// instead of 8 (config B 189.5 vs 194.4 ms, 1/8 slab 29.0 vs 29.4 ms;
-// profiles/r03_coop_ab_configB.json, r03_coop_shard_probe_configB.jsonl)
-[[maybe_unused]] constexpr MfmaSpec kMfmaK5NoTnW4C4 = [] {
-    MfmaSpec x = kMfmaK5NoTnW4;
-    x.tail_lanes = 4;
-    return x;
-}();
-// the 5-product form with workgroup-shared LDS record tiles (rt2_k5_tiles.h):
-// 12 waves (3 per SIMD, one workgroup per CU), K = 4 groups per tile
-constexpr MfmaSpec k5_tiles_spec(int K, bool no_tn, int tail, bool diag = false) {
-    MfmaSpec x = kMfmaK5W4;
-    x.block = 768;
-    x.waves = 3;
-    x.tile_groups = K;
-    x.no_tn = no_tn;
-    x.tail_lanes = tail;
-    x.diag = diag;
-    return x;
-}
-// records resident in LDS (rt2_k5_resident.h): one workgroup per CU (3 or 4
-// waves per SIMD), scenes of <= kResGroups 32-triangle groups
-constexpr int kResGroups = 38;  // 152 KiB of k5 records (4 KiB per group) of the CU's 160 KiB
-constexpr MfmaSpec k5_res_spec(int waves, bool diag = false, int tail = 4) {
-    MfmaSpec x = kMfmaK5NoTn;
-    x.block = 256 * waves;
-    x.waves = waves;
-    x.tail_lanes = tail;
-    x.lane_lds = 0;
-    x.cthr = true;
-    x.lockstep = false;
-    x.thr_hoist = true;  // the threshold fragment once per sweep (config B 158.9 vs 160.2, 166.3 vs 167.5 ms)
-    x.dpp = true;        // the segment's wave maxima by DPP lane moves (159.4 vs 160.4, 163.1 vs 164.6 ms)
-    x.res_groups = kResGroups;
-    x.diag = diag;
-    return x;
-}
-// the threshold in the K-slots (round 6, MfmaSpec::kthr): the resident kernel on the kt records, schedule `sched`;
-// l2: scenes of up to 256 groups, the groups beyond the resident 38 read from L2
-constexpr MfmaSpec kt_res_spec(int sched, bool diag = false, bool l2 = false) {
-    MfmaSpec x = k5_res_spec(4, diag);
-    x.cthr = false;
-    x.thr_hoist = false;
-    x.kthr = sched;
-    x.res_l2 = l2;
-    return x;
-}
-// ... and the LDS-tiled kernel on the kt records (the form of 293), K groups per tile, `waves` per SIMD
-constexpr MfmaSpec kt_tiles_spec(int K, int waves, int sched) {
-    MfmaSpec x = k5_tiles_spec(K, true, 0);
-    x.block = 256 * waves;
-    x.waves = waves;
-    x.rows80 = true;
-    x.lane_lds = 0;
-    x.perm_frag = true;
-    x.dpp = true;
-    x.kthr = sched;
-    return x;
-}
-// the round-6 tiled kernel (above 8,192 triangles): kthr 4, each ray's own W, the tiles streamed with LDS counters
-// (MfmaSpec::tile_flow) and issue priority by finishing rank (flow_prio)
+constexpr int kResL2Groups = 256;  // render_mfma_k5r with res_l2: kResGroups groups resident, the rest from L2
+// records streamed through LDS tiles (rt2_k5_tiles.h): 19-group tiles, each ray's own W, issue priority by
+// finishing rank; 3 waves per SIMD
 constexpr MfmaSpec kt_tiles_flow() {
-    MfmaSpec x = kt_tiles_spec(19, 3, 4);
-    x.kt_lane_w = true;
-    x.tile_flow = true;
-    x.flow_prio = true;
-    return x;
+    return MfmaSpec{.block = 768, .waves = 3, .tail_lanes = 0, .tile_groups = 19, .flow_prio = true, .kt_lane_w = true};
 }
 // ... at 4 waves per SIMD (1,024 threads) with the lean lane state (128 VGPRs, 1 spilled): the default
 constexpr MfmaSpec kt_tiles_flow4() {
@@ -672,22 +576,6 @@ constexpr MfmaSpec kt_tiles_flow4() {
     x.lean = true;
     return x;
 }
-// the round-6 defaults: kthr 4, the lean lane state; l2 = the L2 continuation (39..256 groups), fair = rank slabs
-constexpr MfmaSpec kt_res_lean(bool l2, bool fair, bool lane_w = false) {
-    MfmaSpec x = kt_res_spec(4, false, l2);
-    x.lean = true;
-    x.fair_prio = fair;
-    x.kt_lane_w = lane_w;
-    return x;
-}
-// the whole-image defaults (353, 355): each ray's own W and issue priority by phase (the exact phase and shading
-// above the products: MfmaSpec::phase_prio 4); the rank-slab forms (354, 356) keep fair-share priority instead
-constexpr MfmaSpec kt_res_prod(bool l2) {
-    MfmaSpec x = kt_res_lean(l2, false, true);
-    x.phase_prio = 4;
-    return x;
-}
-constexpr int kResL2Groups = 256;  // render_mfma_k5r with res_l2: 38 groups resident, the rest from L2
 constexpr Bvh3Spec kBvhDefault{.block = 256, .thresh = 16, .slab = Slab::Markstein, .waves = 5, .diag = false};
 
 #ifdef RT2_EXPERIMENTS
@@ -702,129 +590,50 @@ constexpr Bvh3Spec bvh3_x(int t, Slab sl, int w, bool diag = false) {
 }
 #endif
 
-const Variant kVariants[] = {
+constexpr Variant kVariants[] = {
     RT2_VARIANT(0, K_SMEM, render_smem<kSmemDefault>, 256, "smem/256/max3f8/coop32/w6/lockstep"),  // default (<= kSmemMaxTris)
     RT2_VARIANT(109, K_BVH4, render_bvh4<kBvhDefault>, 256, "bvh4/256/t16/w5"),           // default (BVH traversal)
     RT2_VARIANT(86, K_TILED, render_tiled<kTiledLarge>, 512, "tiled/512/max3f4"),          // > kSmemMaxTris
     RT2_VARIANT(92, K_ASSIST, render_assist<kAssist12>, 768, "assist12/max3f8/w6"),        // < 4 items per lane
     RT2_VARIANT(136, K_SMEM, render_smem<kSmemDefault>, 256, "smem/256/max3f8/coop32/w6/lockstep"),  // variant 0 forced (id 0 = automatic)
-    // default brute-force kernel (DESIGN.md "The 5-product form"): the k16 sweep with U, -V, X from the first K-half,
-    // the left-out m.z slots bounded in the threshold; 3 waves per SIMD, and 4 for launches with < 1.5 items per lane
+    // the matrix filter with every wave reading the records from L2 (DESIGN.md "The 5-product form"): U, -V, X from
+    // the first K-half, the left-out m.z slots bounded in the threshold; 3 waves per SIMD
     RT2_VARIANT(227, K_MFMA, render_mfma<kMfmaK5>, 256, "mfma/256/k5/coop8/w3/imax/minred/ymma/t12/llds/ser4/cmp"),
     // scenes of <= 256 groups (8,192 triangles; config B: 38, W: 57, K: 89): the resident kernel (rt2_k5_resident.h:
     // records in LDS for the whole launch, 38 groups, the rest read from L2) with the threshold in the K-slots
-    // (MfmaSpec::kthr 4: 8 independent products per group, the two 32-ray blocks interleaved; DESIGN.md "The
-    // threshold in the K-slots"), the lean lane state; fair-share issue priority for rank slabs
-    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_res_prod(false)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4"),
-    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_res_lean(false, true, true)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw"),
-    RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_res_prod(true)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4"),
-    RT2_VARIANT(356, K_MFMA, render_mfma_k5r<kt_res_lean(true, true, true)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw"),
+    // (DESIGN.md "The threshold in the K-slots"), each ray's own W, issue priority by phase; fair-share issue
+    // priority instead for rank slabs
+    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_res(false, false, true, 4)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
+    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_res(false, true, true)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
+    RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_res(true, false, true, 4)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
+    RT2_VARIANT(356, K_MFMA, render_mfma_k5r<kt_res(true, true, true)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw", kResL2Groups),
     // the default above 8,192 triangles: the LDS-tiled kernel (rt2_k5_tiles.h; 19-group tiles, fragments in
-    // registers) with the threshold in the K-slots, each ray's own W in the bound (round 6; round 5: 293)
+    // registers) with the threshold in the K-slots, each ray's own W in the bound
     RT2_VARIANT(380, K_MFMA, render_mfma_k5t<kt_tiles_flow4()>, 1024, "mfmat5/1024/kt4/tile19/coop0/w4/cmp/regs/perm/lw/flowp/lean"),
 #ifdef RT2_EXPERIMENTS
-    // the tile stream at 3 waves per SIMD (380 takes 4 with the lean lane state)
+    // One knob away from a shipping matrix-filter kernel, plus one diagnostic build per template (DESIGN.md "Tried
+    // and measured"; earlier generations are in git history).
+    // the resident kernel with the wave's W in the bound (353-356 take each ray's own)
+    RT2_VARIANT(342, K_MFMA, render_mfma_k5r<kt_res(false, false, false)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean", kResGroups),
+    RT2_VARIANT(344, K_MFMA, render_mfma_k5r<kt_res(false, true, false)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean", kResGroups),
+    RT2_VARIANT(345, K_MFMA, render_mfma_k5r<kt_res(true, false, false)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean", kResL2Groups),
+    RT2_VARIANT(346, K_MFMA, render_mfma_k5r<kt_res(true, true, false)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean", kResL2Groups),
+    // ... issue priority by phase 1 / 2 / 3 (353 takes 4) and without it; its diagnostic counters
+    RT2_VARIANT(387, K_MFMA, render_mfma_k5r<kt_res(false, false, true, 1)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp1", kResGroups),
+    RT2_VARIANT(388, K_MFMA, render_mfma_k5r<kt_res(false, false, true, 2)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp2", kResGroups),
+    RT2_VARIANT(389, K_MFMA, render_mfma_k5r<kt_res(false, false, true, 3)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp3", kResGroups),
+    RT2_VARIANT(391, K_MFMA, render_mfma_k5r<kt_res(false, false, true)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw", kResGroups),
+    RT2_VARIANT(350, K_MFMA, render_mfma_k5r<kt_res(false, false, true, 0, true)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw", kResGroups),
+    // the tile stream at 3 waves per SIMD (380 takes 4 with the lean lane state): with its diagnostic clocks; without
+    // flow_prio; with the lean lane state
     RT2_VARIANT(370, K_MFMA, render_mfma_k5t<kt_tiles_flow()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp"),
-    // round 6's first tiled default (one workgroup barrier per tile; 370 streams the tiles with LDS counters)
-    RT2_VARIANT(351, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = kt_tiles_spec(19, 3, 4); x.kt_lane_w = true; return x; }()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw"),
-    // round 6's first kthr defaults (the wave's W in the bound; 353-356 take each ray's own)
-    RT2_VARIANT(342, K_MFMA, render_mfma_k5r<kt_res_lean(false, false)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean"),
-    RT2_VARIANT(344, K_MFMA, render_mfma_k5r<kt_res_lean(false, true)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean"),
-    RT2_VARIANT(345, K_MFMA, render_mfma_k5r<kt_res_lean(true, false)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean"),
-    RT2_VARIANT(346, K_MFMA, render_mfma_k5r<kt_res_lean(true, true)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean"),
-    // the defaults of rounds 4-5 (round 6 replaced them by the kthr resident kernels 353-356 and the kthr tiles 351)
-    RT2_VARIANT(293, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = k5_tiles_spec(19, true, 0); x.rows80 = true; x.lane_lds = 0; x.cthr = true; x.perm_frag = true; return x; }()>, 768, "mfmat5/768/k5/notn/tile19/coop0/w3/cmp/regs/cthr/perm"),
-    // (round 4) scenes of <= 8,192 triangles (records L2-resident): the same without the -tn term (4 products per block) and
-    // with the threshold in the products' accumulator (MfmaSpec::cthr, DESIGN.md "The threshold in the
-    // accumulator"), 4 waves (packed path state, Y fragments read per block: 263), or 3 when the packed fields do not
-    // hold the image / rays / bounces (262)
-    RT2_VARIANT(263, K_MFMA, render_mfma<[] { MfmaSpec x = kMfmaK5NoTnW4C4; x.cthr = true; x.ylds = 1; return x; }()>, 256, "mfma/256/k5/notn/coop4/w4/imax/minred/ymma/t12/llds2/ser4/cmp/cthr/yl1"),
-    RT2_VARIANT(262, K_MFMA, render_mfma<[] { MfmaSpec x = kMfmaK5NoTn; x.cthr = true; return x; }()>, 256, "mfma/256/k5/notn/coop8/w3/imax/minred/ymma/t12/llds/ser4/cmp/cthr"),
-    // LDS record tiles shared by the workgroup (rt2_k5_tiles.h; DESIGN.md "LDS record tiles"), the default above
-    // 8,192 triangles: 10-group tiles, path state in registers, the threshold in the accumulator
-    RT2_VARIANT(217, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = k5_tiles_spec(10, true, 0); x.rows80 = true; x.lane_lds = 0; x.cthr = true; return x; }()>, 768, "mfmat5/768/k5/notn/tile10/coop0/w3/cmp/rows80/regs/cthr"),
-    // scenes of <= 38 groups (1,216 triangles: config B): every group's records resident in LDS for the whole
-    // launch (rt2_k5_resident.h), fragments built in registers by v_permlane32_swap, waves run free
-    RT2_VARIANT(282, K_MFMA, render_mfma_k5r<k5_res_spec(4)>, 1024, "mfmar/1024/k5/notn/res38/coop4/w4/cmp/cthr/dpp"),
-    // ... with fair-share issue priority (rank slabs: < kResSlabItems items per lane; DESIGN.md "Fair-share issue
-    // priority")
-    RT2_VARIANT(298, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = k5_res_spec(4); x.fair_prio = true; return x; }()>, 1024, "mfmar/1024/k5/notn/res38/coop4/w4/cmp/cthr/fair/dpp"),
-    // records resident in LDS at 3 waves per SIMD; the resident kernel's diagnostic counters
-    RT2_VARIANT(280, K_MFMA, render_mfma_k5r<k5_res_spec(3)>, 768, "mfmar/768/k5/notn/res38/coop4/w3/cmp/cthr/dpp"),
-    RT2_VARIANT(287, K_MFMA, render_mfma_k5r<k5_res_spec(4, true)>, 1024, "mfmar/1024/k5/notn/res38/coop4/w4/cmp/cthr/diag/dpp"),
-    // the threshold in the K-slots (round 6): schedules 1 (four products, then the reduction) / 2 (cthr's order) /
-    // 3 (no fences); fair-share priority; diagnostic counters; the L2 continuation for 39..256 groups
-    RT2_VARIANT(320, K_MFMA, render_mfma_k5r<kt_res_spec(1)>, 1024, "mfmar/1024/kt1/res38/coop4/w4/cmp/dpp"),
-    RT2_VARIANT(321, K_MFMA, render_mfma_k5r<kt_res_spec(2)>, 1024, "mfmar/1024/kt2/res38/coop4/w4/cmp/dpp"),
-    RT2_VARIANT(322, K_MFMA, render_mfma_k5r<kt_res_spec(3)>, 1024, "mfmar/1024/kt3/res38/coop4/w4/cmp/dpp"),
-    RT2_VARIANT(323, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_spec(1); x.fair_prio = true; return x; }()>, 1024, "mfmar/1024/kt1/res38/coop4/w4/cmp/fair/dpp"),
-    RT2_VARIANT(324, K_MFMA, render_mfma_k5r<kt_res_spec(1, true)>, 1024, "mfmar/1024/kt1/res38/coop4/w4/cmp/diag/dpp"),
-    RT2_VARIANT(325, K_MFMA, render_mfma_k5r<kt_res_spec(1, false, true)>, 1024, "mfmarl2/1024/kt1/res38l2/coop4/w4/cmp/dpp"),
-    // ... at 3 waves per SIMD (168 VGPRs: the four products before the reduction fit), with the next group's
-    // operands read ahead
-    RT2_VARIANT(326, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_spec(1); x.block = 768; x.waves = 3; return x; }()>, 768, "mfmar/768/kt1/res38/coop4/w3/cmp/dpp"),
-    RT2_VARIANT(327, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_spec(1); x.block = 768; x.waves = 3; x.prefetch = true; return x; }()>, 768, "mfmar/768/kt1/res38/coop4/w3/cmp/dpp/pf"),
-    RT2_VARIANT(328, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_spec(1); x.prefetch = true; return x; }()>, 1024, "mfmar/1024/kt1/res38/coop4/w4/cmp/dpp/pf"),
-    // ... schedule 4: the two 32-ray blocks interleaved (each wave's products beside its own reduction)
-    RT2_VARIANT(329, K_MFMA, render_mfma_k5r<kt_res_spec(4)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp"),
-    RT2_VARIANT(336, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_spec(4); x.fair_prio = true; return x; }()>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp"),
-    RT2_VARIANT(337, K_MFMA, render_mfma_k5r<kt_res_spec(4, false, true)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp"),
-    RT2_VARIANT(338, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_spec(4, false, true); x.fair_prio = true; return x; }()>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp"),
-    RT2_VARIANT(339, K_MFMA, render_mfma_k5r<kt_res_spec(4, true)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp"),
-    // ... the fold as two chains (kthr 5); speed-of-light probe without the exact phase (WRONG images: A/B with
-    // --no-check)
-    RT2_VARIANT(340, K_MFMA, render_mfma_k5r<kt_res_spec(5)>, 1024, "mfmar/1024/kt5/res38/coop4/w4/cmp/dpp"),
-    RT2_VARIANT(341, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_spec(4); x.sol = 2; return x; }()>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/sol2"),
-    // ... with the lean lane state (x, y from the item, segments counted per wave)
-    RT2_VARIANT(342, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_spec(4); x.lean = true; return x; }()>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean"),
-    RT2_VARIANT(343, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_spec(5); x.lean = true; return x; }()>, 1024, "mfmar/1024/kt5/res38/coop4/w4/cmp/dpp/lean"),
-    // ... the exact phase with the next triangle requested ahead (vector loads)
-    RT2_VARIANT(347, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_lean(false, false); x.exact_pf = true; return x; }()>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/xpf"),
-    // ... W per ray (kt_lane_w: a tighter threshold, fewer exact tests)
-    RT2_VARIANT(348, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_lean(false, false); x.kt_lane_w = true; return x; }()>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw"),
-    RT2_VARIANT(349, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_lean(false, false); x.kt_lane_w = true; x.exact_pf = true; return x; }()>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/xpf"),
-    RT2_VARIANT(350, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_spec(4, true); x.lean = true; x.kt_lane_w = true; return x; }()>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw"),
-    // ... on the LDS-tiled kernel (the form of 293): 19-group tiles at 3 waves per SIMD (schedules 1, 2), 16-group
-    // tiles at 4 waves
-    RT2_VARIANT(330, K_MFMA, render_mfma_k5t<kt_tiles_spec(19, 3, 1)>, 768, "mfmat5/768/kt1/tile19/coop0/w3/cmp/regs/perm"),
-    RT2_VARIANT(331, K_MFMA, render_mfma_k5t<kt_tiles_spec(19, 3, 2)>, 768, "mfmat5/768/kt2/tile19/coop0/w3/cmp/regs/perm"),
-    RT2_VARIANT(332, K_MFMA, render_mfma_k5t<kt_tiles_spec(19, 3, 4)>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm"),
-    RT2_VARIANT(333, K_MFMA, render_mfma_k5t<kt_tiles_spec(16, 4, 1)>, 1024, "mfmat5/1024/kt1/tile16/coop0/w4/cmp/regs/perm"),
-    RT2_VARIANT(335, K_MFMA, render_mfma_k5t<kt_tiles_spec(16, 4, 4)>, 1024, "mfmat5/1024/kt4/tile16/coop0/w4/cmp/regs/perm"),
-    // ... the tiles as a stream with LDS counters (MfmaSpec::tile_flow): with its diagnostic clocks; without flow_prio
     RT2_VARIANT(368, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = kt_tiles_flow(); x.diag = true; return x; }()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp/diag"),
     RT2_VARIANT(369, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = kt_tiles_flow(); x.flow_prio = false; return x; }()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flow"),
-    // ... 4 waves per SIMD with 16-group tiles; the lean lane state at 3 waves
-    RT2_VARIANT(381, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = kt_tiles_flow4(); x.tile_groups = 16; return x; }()>, 1024, "mfmat5/1024/kt4/tile16/coop0/w4/cmp/regs/perm/lw/flowp/lean"),
     RT2_VARIANT(382, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = kt_tiles_flow(); x.lean = true; return x; }()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp/lean"),
+    // ... 380 with 16-group tiles; without flow_prio; with the cooperative drain at 4
+    RT2_VARIANT(381, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = kt_tiles_flow4(); x.tile_groups = 16; return x; }()>, 1024, "mfmat5/1024/kt4/tile16/coop0/w4/cmp/regs/perm/lw/flowp/lean"),
     RT2_VARIANT(385, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = kt_tiles_flow4(); x.flow_prio = false; return x; }()>, 1024, "mfmat5/1024/kt4/tile19/coop0/w4/cmp/regs/perm/lw/flow/lean"),
     RT2_VARIANT(386, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = kt_tiles_flow4(); x.tail_lanes = 4; return x; }()>, 1024, "mfmat5/1024/kt4/tile19/coop4/w4/cmp/regs/perm/lw/flowp/lean"),
-    // ... issue priority by phase (MfmaSpec::phase_prio 1 / 2 / 3; 353 takes 4); 391 = 353 without it
-    RT2_VARIANT(387, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_lean(false, false, true); x.phase_prio = 1; return x; }()>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp1"),
-    RT2_VARIANT(388, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_lean(false, false, true); x.phase_prio = 2; return x; }()>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp2"),
-    RT2_VARIANT(389, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kt_res_lean(false, false, true); x.phase_prio = 3; return x; }()>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp3"),
-    RT2_VARIANT(391, K_MFMA, render_mfma_k5r<kt_res_lean(false, false, true)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw"),
-    RT2_VARIANT(352, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = kt_tiles_spec(19, 3, 1); x.kt_lane_w = true; return x; }()>, 768, "mfmat5/768/kt1/tile19/coop0/w3/cmp/regs/perm/lw"),
-    RT2_VARIANT(334, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = kt_tiles_spec(19, 3, 1); x.diag = true; return x; }()>, 768, "mfmat5/768/kt1/tile19/coop0/w3/cmp/regs/perm/diag"),
-    RT2_VARIANT(299, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = k5_res_spec(4, true); x.fair_prio = true; return x; }()>, 1024, "mfmar/1024/k5/notn/res38/coop4/w4/cmp/cthr/fair/diag/dpp"),
-    // earlier choices of rounds 3-4 (the 5-product form before and after the threshold moved into the accumulator,
-    // the first tile forms), kept for A/B; rounds 2-3's 16x16x32 and k16 kernels are in git history
-    RT2_VARIANT(231, K_MFMA, render_mfma<kMfmaK5NoTn>, 256, "mfma/256/k5/notn/coop8/w3/imax/minred/ymma/t12/llds/ser4/cmp"),
-    RT2_VARIANT(243, K_MFMA, render_mfma<kMfmaK5NoTnW4C4>, 256, "mfma/256/k5/notn/coop4/w4/imax/minred/ymma/t12/llds2/ser4/cmp"),
-    RT2_VARIANT(213, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = k5_tiles_spec(10, true, 0); x.rows80 = true; x.lane_lds = 0; return x; }()>, 768, "mfmat5/768/k5/notn/tile10/coop0/w3/cmp/rows80/regs"),
-    RT2_VARIANT(252, K_MFMA, render_mfma_k5t<k5_tiles_spec(4, true, 0)>, 768, "mfmat5/768/k5/notn/tile4/coop0/w3/llds2/cmp"),
-    RT2_VARIANT(228, K_MFMA, render_mfma<kMfmaK5W4>, 256, "mfma/256/k5/coop8/w4/imax/minred/ymma/t12/llds2/ser4/cmp"),
-    RT2_VARIANT(233, K_MFMA, render_mfma<kMfmaK5NoTnW4>, 256, "mfma/256/k5/notn/coop8/w4/imax/minred/ymma/t12/llds2/ser4/cmp"),
-    RT2_VARIANT(250, K_MFMA, render_mfma_k5t<k5_tiles_spec(4, false, 0)>, 768, "mfmat5/768/k5/tile4/coop0/w3/llds2/cmp"),
-    RT2_VARIANT(260, K_MFMA, render_mfma<[] { MfmaSpec x = kMfmaK5NoTnW4C4; x.cthr = true; return x; }()>, 256, "mfma/256/k5/notn/coop4/w4/imax/minred/ymma/t12/llds2/ser4/cmp/cthr"),
-    RT2_VARIANT(261, K_MFMA, render_mfma<[] { MfmaSpec x = kMfmaK5NoTnW4C4; x.cthr = true; x.ylds = 2; return x; }()>, 256, "mfma/256/k5/notn/coop4/w4/imax/minred/ymma/t12/llds2/ser4/cmp/cthr/ylds"),
-    RT2_VARIANT(212, K_MFMA, render_mfma_k5t<[] { MfmaSpec x = k5_tiles_spec(8, true, 0); x.rows80 = true; x.lane_lds = 0; return x; }()>, 768, "mfmat5/768/k5/notn/tile8/coop0/w3/cmp/rows80/regs"),
-    RT2_VARIANT(246, K_MFMA, render_mfma<[] { MfmaSpec x = kMfmaK5NoTnW4C4; x.rows80 = true; return x; }()>, 256, "mfma/256/k5/notn/coop4/w4/imax/minred/ymma/t12/llds2/ser4/cmp/rows80"),
-    RT2_VARIANT(251, K_MFMA, render_mfma_k5t<k5_tiles_spec(4, false, 0, true)>, 768, "mfmat5/768/k5/tile4/coop0/w3/llds2/cmp/diag"),
-    // diagnostic builds (group / survivor / exact-test counters, wave timeline)
-    RT2_VARIANT(239, K_MFMA, render_mfma<[] { MfmaSpec x = kMfmaK5NoTnW4; x.diag = true; return x; }()>, 256, "mfma/256/k5/notn/coop8/w4/imax/minred/ymma/t12/llds2/ser4/cmp/diag"),
-    RT2_VARIANT(232, K_MFMA, render_mfma<[] { MfmaSpec x = kMfmaK5NoTn; x.diag = true; return x; }()>, 256, "mfma/256/k5/notn/coop8/w3/imax/minred/ymma/t12/llds/ser4/cmp/diag"),
-    RT2_VARIANT(229, K_MFMA, render_mfma<[] { MfmaSpec x = kMfmaK5; x.diag = true; return x; }()>, 256, "mfma/256/k5/coop8/w3/imax/minred/ymma/t12/llds/ser4/cmp/diag"),
     // scalar-path and BVH kernels of rounds 1-2 (DESIGN.md "Tried and measured"; parity-tested in the experiment build)
     RT2_VARIANT(67, K_SMEM, render_smem<kSmemMid>, 256, "smem/256/max3f8/coop32"),         // round-1 choice, 1-4 items per lane
     RT2_VARIANT(85, K_SPLIT, render_split<kSplitSmall>, 256, "split4/max3f8/w6"),          // round-1 choice, < 1 item per lane
@@ -852,35 +661,29 @@ const Variant kVariants[] = {
                 "smem/256/max3f8/coop32/STATS"),
 #endif
 };
-constexpr size_t kResidentMaxBytes = 112 * 1024;
+constexpr bool variant_ids_unique() {
+    for (const Variant& a : kVariants)
+        for (const Variant& b : kVariants)
+            if (&a != &b && a.id == b.id) return false;
+    return true;
+}
+static_assert(variant_ids_unique(), "two entries of kVariants share an id");
+
 constexpr int kSmemMaxTris = 131072;  // scalar path up to 6.3 MB of records (config C: 781 vs 817 ms tiled; config E: tiled 1,704 vs 2,312 ms)
 constexpr int kDefaultBrute = 0;
 constexpr int kDefaultBvh = 109;
 constexpr int kLargeScene = 86;  // tiled/512/max3f4: LDS tiles above kSmemMaxTris triangles
 constexpr int kSlab = 92;        // assist12/max3f8/w6: fewer than 4 items per lane (multi-GPU slabs)
+// the matrix filter (scenes inside its range; DESIGN.md "The threshold in the K-slots", "LDS record tiles")
 constexpr int kMfmaSlabMaxTris = 8192;  // = kResL2Groups x 32: the resident kernel with its L2 continuation
-constexpr int kMfmaRes = 353;      // <= kResGroups groups (config B): every record resident in LDS, 4 waves per SIMD,
-                                   // the threshold in the K-slots (kthr 4, each ray's own W in the bound), the lean
-                                   // lane state (rt2_k5_resident.h; DESIGN.md "The threshold in the K-slots"): config
-                                   // B 149.0 vs 152.8 ms (342, the wave's W) vs 154.2-165.3 ms for round 5's 282 in
-                                   // A/Bs, identical images
-constexpr int kMfmaResSlab = 354;  // ... launches with < kResSlabItems items per resident lane (rank slabs): the
-                                   // same kernel with fair-share issue priority (MfmaSpec::fair_prio; round 5: 298)
+constexpr int kMfmaRes = 353;      // <= kResGroups groups (config B): every record resident in LDS
+constexpr int kMfmaResSlab = 354;  // ... launches with < kResSlabItems items per resident lane (rank slabs):
+                                   // fair-share issue priority
 constexpr unsigned long long kResSlabItems = 6;
-constexpr int kMfmaResL2 = 355;    // 39..256 groups (configs W, K): 38 groups resident, the rest read from L2
-                                   // (MfmaSpec::res_l2): config W 28.7 vs 46.5 ms, K 306.8 vs 362.1 ms for round 4-5's
-                                   // L2-resident 263 (A/B of the wave-W form 337, identical images)
-constexpr int kMfmaResL2Slab = 356;  // ... its rank slabs (fair-share priority)
-constexpr int kMfmaTiles = 380;    // larger scenes: the LDS-tiled kernel (rt2_k5_tiles.h: one 16-wave workgroup per
-                                   // CU, 19-group record tiles, fragments in registers) with the threshold in the
-                                   // K-slots and each ray's own W (config C sample 962 vs 1,076 ms, config E sample
-                                   // 1,081 vs 1,230 ms for round 5's 293), the tiles streamed with LDS counters and
-                                   // rank priority (full-width config C frame 5,268 vs 5,369 ms, config E 5,447 vs
-                                   // 5,522 ms for 351), 4 waves per SIMD with the lean lane state (C frame 5,037 vs
-                                   // 5,237 ms, E 5,285 vs 5,451 ms for 370; A/B, identical images)
-constexpr int kMfma = 227;  // mfma/.../k5/...: the matrix-core filter on v_mfma_f32_32x32x16_f16, 5 products per
-                            // 32-ray block (DESIGN.md "The 5-product form"), registers only; larger scenes whose
-                            // packed path state cannot hold the launch
+constexpr int kMfmaResL2 = 355;    // 39..256 groups (configs W, K): kResGroups groups resident, the rest read from L2
+constexpr int kMfmaResL2Slab = 356;  // ... its rank slabs
+constexpr int kMfmaTiles = 380;    // larger scenes: the records streamed through LDS tiles, one 16-wave workgroup per CU
+constexpr int kMfma = 227;         // every wave reads the records from L2; taken when kMfmaTiles is not in the build
 
 constexpr bool is_bvh(int kind) { return kind >= K_BVH && kind <= K_BVH4; }
 
@@ -890,7 +693,7 @@ const Variant* find_variant(int id) {
     return nullptr;
 }
 hipError_t variant_occupancy(const Variant& v, int* occ, size_t lds) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, v.kernel, v.block, lds);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, reinterpret_cast<const void*>(v.kernel), v.block, lds);
 }
 }  // namespace
 
@@ -921,7 +724,7 @@ extern "C" int rt2_variant_occupancy(int v, int* api_blocks, int* num_regs, int*
     int occ = 0;
     HIPCHECK(variant_occupancy(*V, &occ, 0));
     hipFuncAttributes a;
-    HIPCHECK(hipFuncGetAttributes(&a, V->kernel));
+    HIPCHECK(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(V->kernel)));
     if (api_blocks) *api_blocks = occ;
     if (num_regs) *num_regs = a.numRegs;
     if (local_bytes) *local_bytes = (int)a.localSizeBytes;
@@ -968,8 +771,6 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
     p.tri = s->d_tri;
     p.plk = s->plk_ok ? s->d_plk : nullptr;
     p.plk_A = s->plk_A;
-    p.mfma_frag = s->d_mfma;
-    p.mfma_tau = s->d_mfma_tau;
     p.mfma_A = s->mfma_A;
     p.mfma_k16_frag = s->d_mfma_k16;
     p.mfma_k16_tau = s->d_mfma_k16_tau;
@@ -1110,24 +911,15 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
         s->cost_npix = p.n_pix;
         std::memcpy(s->cost_key, key, sizeof(key));
     }
-    const size_t resident_bytes = (size_t)3 * sizeof(float4) * (size_t)std::max(s->n_tris, 1);
-    const bool fits = resident_bytes <= kResidentMaxBytes;
-    // explicit variant (rt2_scene_set_variant) when it exists in this build and
-    // matches the traversal; otherwise the automatic choice: the matrix-core
-    // filter kernel for small scenes (config B: 1,208 triangles; the
-    // scalar-path kernel when the scene is outside its range), LDS-tiled sweep
-    // for large ones (config E: 1M triangles)
+    // explicit variant (rt2_scene_set_variant) when it exists in this build,
+    // matches the traversal and can hold the scene; otherwise the automatic
+    // choice: the matrix-core filter kernels (the scalar-path kernel when the
+    // scene is outside the filter's range)
+    const int n_groups = (s->n_tris + 31) / 32;
     const Variant* VP = s->variant > 0 ? find_variant(s->variant) : nullptr;
     if (VP && ((s->traversal == RT2_TRAVERSAL_BVH) != is_bvh(VP->kind))) VP = nullptr;
-    if (VP && VP->kind == K_RESIDENT && !fits) VP = nullptr;  // cannot hold this scene
-    const bool res_fits = (s->n_tris + 31) / 32 <= kResGroups;  // render_mfma_k5r's LDS holds every record group
-    if (VP && !res_fits && std::strncmp(VP->name, "mfmar/", 6) == 0) VP = nullptr;
-    if (VP && (s->n_tris + 31) / 32 > kResL2Groups && std::strncmp(VP->name, "mfmarl2/", 8) == 0) VP = nullptr;
-    if (VP && (VP->kind == K_MFMA || VP->kind == K_MASSIST) && !s->mfma_ok) VP = nullptr;  // scene outside the filter's range
-    // the packed path state (lane_lds = 2) holds 16-bit x, y, rays per pixel and 12-bit bounce counts
-    const bool packed = u->width <= 65535 && u->height <= 65535 && u->maxBounceCount <= 4095 &&
-                        u->numRaysPerPixel <= 65535;
-    if (VP && !packed && std::strstr(VP->name, "llds2")) VP = nullptr;
+    if (VP && VP->max_groups > 0 && n_groups > VP->max_groups) VP = nullptr;  // cannot hold this scene
+    if (VP && VP->kind == K_MFMA && !s->mfma_ok) VP = nullptr;              // scene outside the filter's range
     if (!VP && s->traversal == RT2_TRAVERSAL_BVH) VP = find_variant(kDefaultBvh);
     if (!VP) {
         int vi = s->n_tris <= kSmemMaxTris ? kDefaultBrute : kLargeScene;
@@ -1151,7 +943,7 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
                 // "Fair-share issue priority")
                 const unsigned long long lanes = (unsigned long long)s->num_cus * (unsigned long long)find_variant(kMfmaRes)->block;
                 const bool slab = p.n_items < kResSlabItems * lanes;
-                vi = res_fits ? (slab ? kMfmaResSlab : kMfmaRes) : (slab ? kMfmaResL2Slab : kMfmaResL2);
+                vi = n_groups <= kResGroups ? (slab ? kMfmaResSlab : kMfmaRes) : (slab ? kMfmaResL2Slab : kMfmaResL2);
             } else if (find_variant(kMfmaTiles)) {
                 vi = kMfmaTiles;
             }
@@ -1173,11 +965,6 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
         VP = find_variant(vi);
     }
     const Variant& V = *VP;
-    if (std::strstr(V.name, "f16x3")) {  // the 16x16x32 record layout (experiment variants; built on first use)
-        if (ensure_mfma16(s) != 0) return -1;
-        p.mfma_frag = s->d_mfma;
-        p.mfma_tau = s->d_mfma_tau;
-    }
     // XCD-group item regions serve the BVH walk's L2 locality; the brute-force
     // kernels read the same records for every ray, so they take items from one
     // counter in dispatch order, which spreads neighbouring 64-pixel runs over
@@ -1192,8 +979,6 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
     size_t lds = 0;
     if (V.kind == K_TILED)
         lds = (size_t)3 * sizeof(float4) * kTileTris;
-    else if (V.kind == K_RESIDENT)
-        lds = resident_bytes;
     else if (is_bvh(V.kind)) {
         if (V.kind == K_BVH4) p.stack_slots = std::max(s->bvh_depth, 1);  // next entry in a register
         lds = (size_t)p.stack_slots * V.block * sizeof(int);
@@ -1206,7 +991,7 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
     HIPCHECK(variant_occupancy(V, &occ, lds));
     occ = std::max(occ, 1);
     unsigned long long blocks = (unsigned long long)s->num_cus * occ;
-    if (V.kind == K_ASSIST || V.kind == K_MASSIST) {
+    if (V.kind == K_ASSIST) {
         // every resident workgroup is launched: waves without items help the
         // busy waves of their workgroup.  Below 2 items per lane a quarter of
         // the waves take items (each owner has ~3 helpers; 1/4 and 1/8 slabs
@@ -1215,7 +1000,7 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
         const int nw = V.block / 64;
         const unsigned long long lanes = blocks * (unsigned long long)V.block;
         p.assist_cap = p.n_items < 2 * lanes ? std::max(1, nw / 4) : nw;
-        const int g = V.kind == K_MASSIST ? 16 : 8;  // the sweep's filter group (MFMA: 16-triangle record groups)
+        constexpr int g = 8;  // the sweep's filter group
         int chunk = (s->n_tris + 2 * nw - 1) / (2 * nw);
         chunk = std::max(g, (chunk + g - 1) / g * g);
         p.assist_chunk = chunk;
@@ -1442,8 +1227,8 @@ extern "C" int rt2_device_selftest(const float* in, int32_t n, float* out10) {
 }
 
 // Not in rt2.h (test hook): copies one of the scene's derived device arrays to
-// host memory: 0 = pre-transformed triangles (3 float4 each), 1 = render_mfma
-// records (16x16x32 layout), 2 = their per-triangle tau, 3 = sweep_k16 records,
+// host memory: 0 = pre-transformed triangles (3 float4 each), 1 = the filter
+// records in the 16x16x32 layout, 2 = their per-triangle tau, 3 = sweep_k16 records,
 // 4 = their tau, 5 = the k5 form's per-triangle m.z residual bounds, 6 = the
 // kthr records (threshold in the K-slots).  Returns the array's size in bytes (nothing copied when
 // `host` is null or `bytes` is too small), < 0 on error.
@@ -1476,14 +1261,13 @@ extern "C" long long rt2_scene_export(rt2_scene* s, int what, void* host, unsign
 // Not in rt2.h (test hook): the matrix filter's terms on the hardware
 // (mfma_probe_kernel) for n_rays rays (a multiple of 64; 8 floats each: o.xyz,
 // best, d.xyz, 0) against every triangle of the scene.  layout 0 = the
-// 16x16x32 form of render_mfma (variants 150/152), 1 = the k16 form
-// (sweep_k16), 2 = its 5-product form (MfmaSpec::k5: U, -V, X from the first
-// K-half), 3 = the 5-product form with the threshold in the accumulator
-// (MfmaSpec::cthr: U, -V, X, Y shifted by TT = -Tl'', TT in the -tn slot),
-// 4 = layout 3 with the fragments built in registers by frag_pair (the
-// operand path of 282 / 293 / 298), 5 = the threshold in the K-slots
-// (MfmaSpec::kthr, frag_pair fragments: U, -V, X, Y, slot 3 zero), 6 = layout
-// 5 with each ray's own W (MfmaSpec::kt_lane_w).
+// 16x16x32 form, 1 = the 8-product k16 form, 2 = its 5-product form
+// (sweep_k16: U, -V, X from the first K-half), 3 = the 5-product form with the
+// threshold in the accumulator (U, -V, X, Y shifted by TT = -Tl'', TT in the
+// -tn slot), 4 = layout 3 with the fragments built in registers by frag_pair,
+// 5 = the threshold in the K-slots (render_mfma_k5r / render_mfma_k5t,
+// frag_pair fragments: U, -V, X, Y, slot 3 zero), 6 = layout 5 with each
+// ray's own W (MfmaSpec::kt_lane_w).
 // Host outputs, sized by the caller: terms [n_rays][n_pad][5]
 // (n_pad = triangles padded to 16 / 32), frags [n_rays][80] f16 bits (the LDS
 // row of layouts 0..3: main slots 0..31 and Y slots 16..31; layouts 4, 5 also
@@ -1526,58 +1310,19 @@ extern "C" int rt2_mfma_probe(rt2_scene* s, int layout, const float* rays, int32
         p.mfma_k16_tau = s->d_mfma_k16_tau;
         p.mfma_k16_bnd = s->d_mfma_k16_bnd;
         p.mfma_kt_frag = s->d_mfma_kt;
-        constexpr MfmaSpec k16 = k16_spec(3), f16x32 = kMfmaT8Y4;
-        constexpr MfmaSpec k5 = [] {
-            MfmaSpec x = k16_spec(3);
-            x.k5 = true;
-            return x;
-        }();
-        constexpr MfmaSpec k5c = [] {
-            MfmaSpec x = k16_spec(3);
-            x.k5 = true;
-            x.no_tn = true;
-            x.cthr = true;
-            return x;
-        }();
-        // the shipping operand path: fragments by frag_pair (v_permlane32_swap), cthr (282 / 293 / 298) or
-        // kthr (the threshold in the K-slots)
-        constexpr MfmaSpec k5cp = [] {
-            MfmaSpec x = k5_res_spec(4);
-            x.perm_frag = true;
-            return x;
-        }();
-        constexpr MfmaSpec ktp = [] {
-            MfmaSpec x = kt_res_spec(1);
-            x.perm_frag = true;
-            return x;
-        }();
-        constexpr MfmaSpec ktpl = [] {
-            MfmaSpec x = kt_res_spec(1);
-            x.perm_frag = true;
-            x.kt_lane_w = true;
-            return x;
-        }();
-        if (layout == 4)
-            hipLaunchKernelGGL(mfma_probe_kernel<k5cp>, dim3(n_rays / 64), dim3(64), 0, 0, p, d_rays, n_pad, d_terms,
-                               d_frags, d_info, d_acc);
-        else if (layout == 5)
-            hipLaunchKernelGGL(mfma_probe_kernel<ktp>, dim3(n_rays / 64), dim3(64), 0, 0, p, d_rays, n_pad, d_terms,
-                               d_frags, d_info, d_acc);
-        else if (layout == 6)
-            hipLaunchKernelGGL(mfma_probe_kernel<ktpl>, dim3(n_rays / 64), dim3(64), 0, 0, p, d_rays, n_pad, d_terms,
-                               d_frags, d_info, d_acc);
-        else if (layout == 3)
-            hipLaunchKernelGGL(mfma_probe_kernel<k5c>, dim3(n_rays / 64), dim3(64), 0, 0, p, d_rays, n_pad, d_terms,
-                               d_frags, d_info, d_acc);
-        else if (layout == 1)
-            hipLaunchKernelGGL(mfma_probe_kernel<k16>, dim3(n_rays / 64), dim3(64), 0, 0, p, d_rays, n_pad, d_terms,
-                               d_frags, d_info, d_acc);
-        else if (layout == 2)
-            hipLaunchKernelGGL(mfma_probe_kernel<k5>, dim3(n_rays / 64), dim3(64), 0, 0, p, d_rays, n_pad, d_terms,
-                               d_frags, d_info, d_acc);
-        else
-            hipLaunchKernelGGL(mfma_probe_kernel<f16x32>, dim3(n_rays / 64), dim3(64), 0, 0, p, d_rays, n_pad,
-                               d_terms, d_frags, d_info, d_acc);
+        const auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(n_rays / 64), dim3(64), 0, 0, p, d_rays, n_pad, d_terms, d_frags, d_info,
+                               d_acc);
+        };
+        switch (layout) {
+        case 0: launch(mfma_probe_kernel<0>); break;
+        case 1: launch(mfma_probe_kernel<1>); break;
+        case 2: launch(mfma_probe_kernel<2>); break;
+        case 3: launch(mfma_probe_kernel<3>); break;
+        case 4: launch(mfma_probe_kernel<4>); break;
+        case 5: launch(mfma_probe_kernel<5>); break;
+        default: launch(mfma_probe_kernel<6>); break;
+        }
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipDeviceSynchronize());
         HIPCHECK(hipMemcpy(terms, d_terms, b_terms, hipMemcpyDeviceToHost));

@@ -1,4 +1,4 @@
-"""Filter survivor statistics of the brute sweeps (diagnostic variants 81/82):
+"""Filter survivor statistics of the brute sweeps (diagnostic variant 82):
 per wave-test, how often some lane passes the division-free filter (and the
 wave enters the exact path), and the lane-level survivor rate."""
 import argparse
@@ -15,7 +15,7 @@ import rt2  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="B")
-ap.add_argument("--variants", default="82,81")
+ap.add_argument("--variants", default="82")
 ap.add_argument("--width", type=int, default=480)
 ap.add_argument("--height", type=int, default=270)
 a = ap.parse_args()

@@ -7,7 +7,7 @@
 #   TESTK="<expr>"   ... and this -k expression
 #   AB="<cfg>:<variants>[:<rounds>[:<extra>]] ..."
 #                    interleaved A/B (scripts/ab_variants.py), identical images required;
-#                    e.g. AB="B:282,320:5 C:293,330:1:--width 480 --height 270 --frames 2"
+#                    e.g. AB="B:353,342:5 C:380,370:1:--width 480 --height 270 --frames 2"
 #   STATSV="<cfg>:<variants> ..."   diagnostic counters (scripts/mfma_stats.py)
 #   SHARD="<cfg>[:<variants>] ..."  every rank's slab on one GPU (scripts/shard_probe.py)
 #   BENCH="<args>"   python bench.py <args> -> bench_<TAG>.json in the output folder

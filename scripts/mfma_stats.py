@@ -1,7 +1,8 @@
-"""Matrix-filter survivor statistics (diagnostic variants 147 / 151 = the
-matrix kernels 140 / 150 (the default) plus counters; experiment build, RT2_LIB=exp): per
-(wave, 16-triangle group) sweep, how often a pair passes the filter (the wave
-enters the exact phase) and how many (wave, triangle) exact tests follow."""
+"""Matrix-filter survivor statistics (diagnostic variants 350 / 368 = the
+resident kernel 391 and the tile stream 370 plus counters; experiment build,
+RT2_LIB=exp): per (wave, 32-triangle group) sweep, how often a pair passes the
+filter (the wave enters the exact phase) and how many (wave, triangle) exact
+tests follow."""
 import argparse
 import ctypes as C
 import json
@@ -16,7 +17,7 @@ import rt2  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="B")
-ap.add_argument("--variants", default="150,151")
+ap.add_argument("--variants", default="391,350")
 ap.add_argument("--width", type=int, default=1920)
 ap.add_argument("--height", type=int, default=1080)
 a = ap.parse_args()
@@ -42,7 +43,7 @@ for v in [int(x) for x in a.variants.split(",")]:
         ms=round(dt * 1e3, 1), segments=st.segments, wave_groups=groups,
         hot_group_rate=hot / max(groups, 1), exact_tests_per_group=exact / max(groups, 1),
         exact_tests_per_hot_group=exact / max(hot, 1),
-        wave_triangle_exact_rate=exact / max(16 * groups, 1))
+        wave_triangle_exact_rate=exact / max(32 * groups, 1))
 vs = list(imgs)
 res["bit_identical"] = all(bool((imgs[v] == imgs[vs[0]]).all()) for v in vs[1:])
 print(json.dumps(res, indent=1))

@@ -409,8 +409,8 @@ def test_frame_split_identical(rt2mod, oraclemod, config_scene, torch_cuda, trav
 # variants (masked/plk filters, resident LDS, cooperative and team tail modes,
 # split waves, the round-1 slab kernels, occupancy hints)
 BRUTE_VARIANTS = [0, 86, 92, 227, 380, 353, 354, 355, 356, 136] + (
-    [217, 262, 263, 282, 298, 213, 231, 243, 252, 260, 261, 212, 246, 228, 233, 250, 280, 320, 321, 322, 323, 325, 326,
-     327, 328, 329, 336, 337, 338, 340, 343, 351, 369, 370, 67, 85, 106, 64, 66, 74, 76, 79, 80] if EXPERIMENTS else [])
+    [342, 344, 345, 346, 350, 387, 388, 389, 391, 368, 369, 370, 381, 382, 385, 386, 67, 85, 106, 64, 66, 74, 76, 79,
+     80] if EXPERIMENTS else [])
 
 
 @pytest.mark.parametrize("variant", BRUTE_VARIANTS)
