@@ -49,7 +49,7 @@ __device__ __forceinline__ float smoothstep(float e0, float e1, float x) {
 // div_scale/div_fixup range handling).  rcp_variant(x, 3) is bit-identical to
 // IEEE 1.0f/x for every x whose reciprocal is a normal number — checked
 // exhaustively on the device over all such bit patterns
-// (tests/test_gpu_numerics.py::test_rcp_exhaustive).
+// (tests/test_gpu_rcp_exact.py).
 __device__ __forceinline__ float rcp_variant(float x, int v) {
     float r = __builtin_amdgcn_rcpf(x);
     if (v == 0) return r;
@@ -72,16 +72,28 @@ __device__ __forceinline__ float rnd(uint32_t& state) {
     return (float)r / 4294967296.0f;
 }
 
-// randomDirection, compute.glsl:174-185
+// randomDirection, compute.glsl:174-185.  The reference accepts p when
+// length(p) = sqrt(s) < 1 with s = dot(p, p) >= 0; the loop tests s < 1 and
+// the square root is taken once, after it, on the accepted s (a wave stays in
+// the loop until its slowest lane accepts).  The two tests agree:
+//   s < 1  => s <= 1 - 2^-24, and sqrt(1 - 2^-24) = 1 - 2^-25 - 2^-51 - ...
+//             lies below the midpoint 1 - 2^-25, so it rounds to 1 - 2^-24;
+//             correctly rounded sqrt is monotone, so sqrt(s) <= 1 - 2^-24 < 1;
+//   s >= 1 => sqrt(s) >= sqrt(1) = 1 by the same monotonicity.
 __device__ __forceinline__ f3 rnd_dir(uint32_t& state) {
-    for (int i = 0; i < 100; i++) {
+    f3 p = mk(0.0f, 0.0f, 0.0f);
+    float s = 0.0f;
+    bool ok = false;
+    for (int i = 0; i < 100 && !ok; i++) {
         float x = rnd(state) * 2.0f - 1.0f;
         float y = rnd(state) * 2.0f - 1.0f;
         float z = rnd(state) * 2.0f - 1.0f;
-        f3 p = mk(x, y, z);
-        if (length(p) < 1.0f) return normalize(p);
+        p = mk(x, y, z);
+        s = dot(p, p);
+        ok = s < 1.0f;
     }
-    return mk(0.0f, 0.0f, 0.0f);
+    if (!ok) return mk(0.0f, 0.0f, 0.0f);
+    return divs(p, __builtin_sqrtf(s));  // normalize(p)
 }
 
 // refract_, compute.glsl:201-214

@@ -219,6 +219,17 @@ __global__ void prep_triangles(const rt2_triangle* tris, int n, float4* out, int
     mtl[i] = t.materialIndex;
 }
 
+// The unit normal shade() scatters about, once per triangle instead of once
+// per hit: normalize(cross01) (compute.glsl:331) by the same normalize on the
+// same stored normal, so the bits are those shade() computed before.
+__global__ void prep_unit_normals(const float4* tri, int n, float4* out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 t2 = tri[3 * i + 2];
+    const f3 u = normalize(mk(t2.y, t2.z, t2.w));
+    out[i] = make_float4(u.x, u.y, u.z, 0.0f);
+}
+
 // sweep_plk records (rt2_sweep.h) from the pre-transformed triangles, in
 // binary64: p0 = a×e0, p1 = a×e1 and a·n are rounded once to binary32 after
 // the exact power-of-two scale s (s·max(|e0|,|e1|,|n|)∞ in [1,2)).  The

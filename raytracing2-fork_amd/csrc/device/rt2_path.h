@@ -237,8 +237,8 @@ __device__ __forceinline__ void shade(Lane& L, const RenderParams& p, float best
         // segment's own origin, which the scatter below overwrites)
         f3 tex = mk(0.0f, 0.0f, 0.0f);
         if (p.mats[mi].materialType == RT2_TEXTURE) tex = texture_color(p, p.mats[mi].textureIndex, bi, L.o, L.d);
-        const float4 t2 = p.tri[3 * bi + 2];
-        const f3 normal = normalize(mk(t2.y, t2.z, t2.w));  // normalize(cross01), compute.glsl:331
+        const float4 un = p.unit_n[bi];
+        const f3 normal = mk(un.x, un.y, un.z);         // normalize(cross01), compute.glsl:331 (prep_unit_normals)
         const f3 hitPoint = add(L.o, muls(L.d, best));      // compute.glsl:330
         const rt2_material m = p.mats[mi];
         if (m.materialType != RT2_GLASS)

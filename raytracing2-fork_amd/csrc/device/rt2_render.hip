@@ -66,6 +66,7 @@ struct rt2_scene {
     int n_tris = 0, n_mats = 0, n_nodes = 0;
     rt2_triangle* d_raw = nullptr;
     float4* d_tri = nullptr;
+    float4* d_unit_n = nullptr;                 // per-triangle unit normal (prep_unit_normals)
     int* d_mtl = nullptr;
     rt2_material* d_mats = nullptr;
     rt2_node* d_nodes = nullptr;
@@ -363,6 +364,7 @@ static int scene_init(rt2_scene* s, const rt2_triangle* tris, int32_t n_tris, co
     const size_t nt = (size_t)std::max(n_tris, 1);
     HIPCHECK(hipMalloc(&s->d_raw, nt * sizeof(rt2_triangle)));
     HIPCHECK(hipMalloc(&s->d_tri, nt * 3 * sizeof(float4)));
+    HIPCHECK(hipMalloc(&s->d_unit_n, nt * sizeof(float4)));
     HIPCHECK(hipMalloc(&s->d_mtl, nt * sizeof(int)));
     HIPCHECK(hipMalloc(&s->d_mats, (size_t)n_mats * sizeof(rt2_material)));
     HIPCHECK(hipMalloc(&s->d_counters, kCounters * sizeof(unsigned long long)));
@@ -397,6 +399,9 @@ static int scene_init(rt2_scene* s, const rt2_triangle* tris, int32_t n_tris, co
     if (n_tris > 0) {
         hipLaunchKernelGGL(prep_triangles, dim3((n_tris + 255) / 256), dim3(256), 0, 0, s->d_raw, n_tris, s->d_tri,
                            s->d_mtl);
+        HIPCHECK(hipGetLastError());
+        hipLaunchKernelGGL(prep_unit_normals, dim3((n_tris + 255) / 256), dim3(256), 0, 0, s->d_tri, n_tris,
+                           s->d_unit_n);
         HIPCHECK(hipGetLastError());
 #ifdef RT2_EXPERIMENTS
         HIPCHECK(hipMalloc(&s->d_plk, nt * 4 * sizeof(float4)));
@@ -468,6 +473,7 @@ extern "C" void rt2_scene_destroy(rt2_scene* s) {
     (void)hipSetDevice(s->device);
     (void)hipFree(s->d_raw);
     (void)hipFree(s->d_tri);
+    (void)hipFree(s->d_unit_n);
     (void)hipFree(s->d_mtl);
     (void)hipFree(s->d_mats);
     (void)hipFree(s->d_nodes);
@@ -769,6 +775,7 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
     RenderParams p;
     std::memset(&p, 0, sizeof(p));
     p.tri = s->d_tri;
+    p.unit_n = s->d_unit_n;
     p.plk = s->plk_ok ? s->d_plk : nullptr;
     p.plk_A = s->plk_A;
     p.mfma_A = s->mfma_A;

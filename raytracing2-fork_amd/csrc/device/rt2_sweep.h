@@ -24,6 +24,7 @@ enum class Tail : int {
 
 struct RenderParams {
     const float4* tri;  // 3 float4 per triangle: {ax ay az e0x} {e0y e0z e1x e1y} {e1z nx ny nz}
+    const float4* unit_n;  // per triangle: normalize(n) in xyz (prep_unit_normals), read by shade()
     const int* tri_mtl;
     const rt2_material* mats;
     int n_tris;
