@@ -10,7 +10,10 @@ old (or at once when forced) and issues the wave's next share once every wave
 has released that tile's buffer (rel[b] == NW * (s // NB)).  A share's DMA
 lands after a random delay; publishing waits for it (s_waitcnt vmcnt(0)).
 Segments are nt consecutive stream indices separated by a workgroup vote
-(barrier), as in render_mfma_k5t.
+(barrier), as in render_mfma_k5t.  A wave without rays in a segment (compute
+== false: no rays, or the cooperative drain) does not sweep: it skips the
+group loop, with its age++ and in-loop upkeep, and goes from the landed-wait
+straight to the release; each wave draws that flag at random per segment.
 
 Random interleavings of the waves (one atomic step at a time) check the two
 safety properties the kernel relies on and that every run terminates:
@@ -25,8 +28,10 @@ import pytest
 
 
 class Model:
-    def __init__(self, nw, nb, k, ng, segments, seed, check_release=True):
+    def __init__(self, nw, nb, k, ng, segments, seed, check_release=True, idle=0.0):
         self.nw, self.nb, self.k, self.ng = nw, nb, k, ng
+        self.idle = idle  # probability that a wave does not sweep in a segment
+        self.swept = []   # the flag of every (wave, segment) pair, in the order drawn
         self.nt = (ng + k - 1) // k
         self.segments = segments
         self.rng = random.Random(seed)
@@ -104,6 +109,8 @@ class Model:
             while not self.barrier_open(seg):
                 yield
             W = self.waves[w]
+            compute = self.idle <= 0.0 or self.rng.random() >= self.idle
+            self.swept.append(compute)
             for t in range(self.nt):
                 s = W["next"]
                 W["next"] += 1
@@ -116,7 +123,7 @@ class Model:
                 assert all(x == s for x in self.buf_tile[b]), f"wave {w} reads tile {s} before it landed"
                 W["cur"] = s
                 self.reading[b].add(w)
-                for gi in range(gn):
+                for gi in range(gn if compute else 0):
                     W["age"] += 1
                     yield from upkeep(False, gi == k // 2)
                     assert all(x == s for x in self.buf_tile[b]), f"buffer {b} overwritten under wave {w}"
@@ -139,11 +146,33 @@ class Model:
         return len(self.arrived.get(seg, ())) == self.nw
 
 
-@pytest.mark.parametrize("nw,nb,k,ng,segments", [(16, 2, 19, 60, 3), (12, 2, 19, 19, 3), (4, 2, 3, 10, 4),
-                                                  (8, 4, 2, 9, 3), (2, 2, 1, 1, 5), (6, 2, 4, 23, 2)])
+# the last three: a last tile of gn <= k // 2 groups (no mid-tile issue: gi ==
+# k // 2 is never reached; 28 = 19 + 9 groups, and a single group), and an odd
+# tile count with 16 waves (57 = 3 x 19: the same tile alternates between the
+# buffers from segment to segment)
+SETS = [(16, 2, 19, 60, 3), (12, 2, 19, 19, 3), (4, 2, 3, 10, 4), (8, 4, 2, 9, 3), (2, 2, 1, 1, 5), (6, 2, 4, 23, 2),
+        (16, 2, 19, 28, 4), (16, 2, 19, 1, 5), (16, 2, 19, 57, 3)]
+
+
+@pytest.mark.parametrize("nw,nb,k,ng,segments", SETS)
 def test_tile_stream_safe_and_terminates(nw, nb, k, ng, segments):
     for seed in range(30):
         Model(nw, nb, k, ng, segments, seed).run()
+
+
+# some, most and all (wave, segment) pairs idle
+@pytest.mark.parametrize("idle", [0.3, 0.7, 1.0])
+@pytest.mark.parametrize("nw,nb,k,ng,segments", SETS)
+def test_tile_stream_with_idle_waves_safe_and_terminates(nw, nb, k, ng, segments, idle):
+    for seed in range(30):
+        Model(nw, nb, k, ng, segments, seed, idle=idle).run()
+
+
+def test_idle_waves_are_drawn():
+    """The flag is really drawn: with idle = 0.5 some (wave, segment) pairs sweep and some do not."""
+    m = Model(16, 2, 19, 28, 4, 0, idle=0.5)
+    m.run()
+    assert len(m.swept) == 16 * 4 and 0 < sum(m.swept) < len(m.swept)
 
 
 def test_tile_stream_mutant_without_release_check_is_caught():
@@ -151,6 +180,17 @@ def test_tile_stream_mutant_without_release_check_is_caught():
     for seed in range(20):
         try:
             Model(4, 2, 3, 10, 3, seed, check_release=False).run()
+        except AssertionError:
+            caught += 1
+    assert caught > 0
+
+
+@pytest.mark.parametrize("idle", [0.3, 0.7])
+def test_tile_stream_mutant_is_caught_with_idle_waves(idle):
+    caught = 0
+    for seed in range(20):
+        try:
+            Model(4, 2, 3, 10, 3, seed, check_release=False, idle=idle).run()
         except AssertionError:
             caught += 1
     assert caught > 0
