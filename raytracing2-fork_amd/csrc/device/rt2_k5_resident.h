@@ -28,6 +28,23 @@
 // the exact phase is the reference arithmetic in index order, so the image is
 // the sequential strict `dst < best` scan's bit for bit.  Reference:
 // compute.glsl:429-434 (the `triangles[i]` loop this sweep replaces).
+//
+// The exact phase runs once per window of MfmaSpec::exact_win groups, not
+// once per hot group: the window's products run back to back (no branch, no
+// priority flip, no Y rebuild between its groups), each group's 32-bit hot
+// mask is parked in a lane of one VGPR, and one episode then tests the
+// window's survivors, groups ascending and indices ascending within a group,
+// and rebuilds Y once if a bound improved and groups remain (never after the
+// sweep's last group).  The shipped kernels take a window of kResGroups: the
+// resident sweep is one stretch of products and one episode; the L2 loop's
+// windows start again at group kResGroups.
+// Why this is exact: inside a window the Y fragment carries the bound the
+// window started with, which is >= the bound the per-group form would use at
+// each of its groups.  The filter's guarantee is that it never rejects a pair
+// the reference would accept under the bound it was given, and a looser bound
+// only passes more pairs; those are decided by mt_pass3 / mt_exact against the
+// current bound, in index order, like every other survivor.  The price is
+// more tests (config B: 0.686 per (wave, group) against 0.634).
 #pragma once
 
 namespace {
@@ -39,8 +56,8 @@ struct K5Resident {
     h8 rec[kResGroups * 4 * 64];
 };
 
-// The exact phase of one group: the triangles with a passing pair (ballot M)
-// in index order, mt_pass3 + mt_exact (compute.glsl:302-340, strict `dst <
+// The exact phase of one group (exact_win = 1, the A/B arms' per-group form):
+// the triangles with a passing pair (ballot M) in index order, mt_pass3 + mt_exact (compute.glsl:302-340, strict `dst <
 // best`).  Returns whether some lane's bound improved.
 template <MfmaSpec S>
 __device__ __forceinline__ bool exact_group(unsigned long long M, int G, int n_tris, cfloat* tri, const f3& o,
@@ -59,6 +76,52 @@ __device__ __forceinline__ bool exact_group(unsigned long long M, int G, int n_t
         if (mt_pass3(qq, bestK)) mt_exact(qq, idx, best, bi, bestK);
     }
     return __ballot(bestK != bk0) != 0;
+}
+
+// The exact episode of one window of cnt groups from group Gw on: group Gw +
+// j's hot mask is lane j of maskv (exact_win = 1: m1).  The groups in
+// ascending order, each mask's triangles in ascending index, the same tests as
+// exact_group; then one Y rebuild if some lane's bound improved and `more`
+// groups follow.  diag: of the episode's clocks, the wait for the first survivor's
+// triangle (a touch of its first word; the test's own loads then hit the
+// scalar cache) goes to dg.t_issue and the rebuild to dg.t_pub.
+template <MfmaSpec S, class Rebuild>
+__device__ __forceinline__ void exact_window(uint32_t m1, int maskv, int Gw, int cnt, bool more, int n_tris,
+                                             cfloat* tri, const f3& o, const f3& d, float& best, int& bi,
+                                             float& bestK, MfmaDiag& dg, Rebuild rebuild) {
+    constexpr int W = S.exact_win;
+    auto mask_of = [&](int j) { return W == 1 ? m1 : (uint32_t)__builtin_amdgcn_readlane(maskv, j); };
+    [[maybe_unused]] unsigned long long tc = 0;
+    if constexpr (S.diag) {
+        dg.claims += 1;
+        tc = __builtin_amdgcn_s_memtime();
+        int j = 0;
+        while (!mask_of(j)) j++;  // the caller saw a non-zero mask
+        const int idx = 32 * (Gw + j) + __builtin_ctz(mask_of(j));
+        if (idx < n_tris) asm volatile("" ::"s"(__float_as_int(tri[12 * idx])));
+        const unsigned long long t = __builtin_amdgcn_s_memtime();
+        dg.t_issue += t - tc;
+    }
+    const float bk0 = bestK;
+    for (int j = 0; j < cnt; j++) {
+        uint32_t m32 = mask_of(j);
+        if constexpr (S.diag) dg.hot += m32 != 0;
+        while (m32) {
+            const int tt = __builtin_ctz(m32);
+            m32 &= m32 - 1;
+            const int idx = 32 * (Gw + j) + tt;
+            if (idx >= n_tris) break;
+            if constexpr (S.diag) dg.exact += 1;
+            cfloat* tp = tri + 12 * idx;
+            const MtQ qq = mt_quantities(o, d, ldc4(tp), ldc4(tp + 4), ldc4(tp + 8));
+            if (mt_pass3(qq, bestK)) mt_exact(qq, idx, best, bi, bestK);
+        }
+    }
+    if (more && __ballot(bestK != bk0)) {
+        if constexpr (S.diag) tc = __builtin_amdgcn_s_memtime();
+        rebuild();
+        if constexpr (S.diag) dg.t_pub += __builtin_amdgcn_s_memtime() - tc;
+    }
 }
 
 // MfmaSpec::phase_prio: the wave's issue priority by its phase (the SIMD's
@@ -110,28 +173,61 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
     const int nres = S.res_l2 ? min(ng, kResGroups) : ng;
     cfloat* const tri = (cfloat*)p.tri;  // held across the sweep (not re-read from the kernel arguments per hot group)
     const h8* tb = rec + lane;
-    for (int G = 0; G < nres; G++) {
-        const h8 b0 = tb[0], b1 = tb[64], b2 = tb[128], b3 = tb[192];
-        tb += kKtOps * 64;
-        const unsigned long long M = kt_group(a0, y1, b0, b1, b2, b3, upper);
-        if constexpr (S.diag) dg.groups += 1;
-        stamp(dg.t_filt);
-        if (M) {
-            phase_prio<S>(1);
-            if (exact_group<S>(M, G, n_tris, tri, o, d, best, bi, bestK, dg)) kt_y(d, o, bestK, sc, tw16, y1);
-            phase_prio<S>(0);
-        }
-        stamp(dg.t_exact);
-    }
-    if constexpr (S.res_l2) {
-        const h8* gb = reinterpret_cast<const h8*>(p.mfma_kt_frag) + (size_t)nres * (kKtOps * 64) + lane;
-        for (int G = nres; G < ng; G++) {
-            const h8 b0 = gb[0], b1 = gb[64], b2 = gb[128], b3 = gb[192];
-            gb += kKtOps * 64;
+    if constexpr (S.exact_win == 1 && !S.y_skip_last && !S.diag) {
+        // one exact episode per hot group, the bound rebuilt after each
+        for (int G = 0; G < nres; G++) {
+            const h8 b0 = tb[0], b1 = tb[64], b2 = tb[128], b3 = tb[192];
+            tb += kKtOps * 64;
             const unsigned long long M = kt_group(a0, y1, b0, b1, b2, b3, upper);
-            if constexpr (S.diag) dg.groups += 1;
-            if (M && exact_group<S>(M, G, n_tris, tri, o, d, best, bi, bestK, dg)) kt_y(d, o, bestK, sc, tw16, y1);
+            if (M) {
+                phase_prio<S>(1);
+                if (exact_group<S>(M, G, n_tris, tri, o, d, best, bi, bestK, dg)) kt_y(d, o, bestK, sc, tw16, y1);
+                phase_prio<S>(0);
+            }
         }
+        if constexpr (S.res_l2) {
+            const h8* gb = reinterpret_cast<const h8*>(p.mfma_kt_frag) + (size_t)nres * (kKtOps * 64) + lane;
+            for (int G = nres; G < ng; G++) {
+                const h8 b0 = gb[0], b1 = gb[64], b2 = gb[128], b3 = gb[192];
+                gb += kKtOps * 64;
+                const unsigned long long M = kt_group(a0, y1, b0, b1, b2, b3, upper);
+                if (M && exact_group<S>(M, G, n_tris, tri, o, d, best, bi, bestK, dg)) kt_y(d, o, bestK, sc, tw16, y1);
+            }
+        }
+    } else {
+        constexpr int W = S.exact_win;
+        static_assert(W >= 1 && W <= 64, "a window's masks are the lanes of one VGPR");
+        // One loop of windows over the groups [G0, G1), records at tb (LDS
+        // or L2): the window's products back to back, each group's hot mask
+        // kept in lane (G - window start) of maskv, then one episode.
+        auto windows = [&](const h8* tb, int G0, int G1, bool resident) {
+            for (int Gw = G0; Gw < G1; Gw += W) {
+                const int cnt = W == 1 ? 1 : min(W, G1 - Gw);
+                int maskv = 0;
+                uint32_t any = 0;
+                for (int j = 0; j < cnt; j++) {
+                    const h8 b0 = tb[0], b1 = tb[64], b2 = tb[128], b3 = tb[192];
+                    tb += kKtOps * 64;
+                    const unsigned long long M = kt_group(a0, y1, b0, b1, b2, b3, upper);
+                    const uint32_t m32 = (uint32_t)(M | M >> 32);
+                    if constexpr (W > 1) maskv = lane == j ? (int)m32 : maskv;
+                    any |= m32;
+                }
+                if constexpr (S.diag) dg.groups += (unsigned long long)cnt;
+                if (resident) stamp(dg.t_filt);
+                if (any) {
+                    const bool more = Gw + cnt < ng || (W == 1 && !S.y_skip_last);
+                    if (resident) phase_prio<S>(1);
+                    exact_window<S>(any, maskv, Gw, cnt, more, n_tris, tri, o, d, best, bi, bestK, dg,
+                                    [&] { kt_y(d, o, bestK, sc, tw16, y1); });
+                    if (resident) phase_prio<S>(0);
+                }
+                if (resident) stamp(dg.t_exact);
+            }
+        };
+        windows(tb, 0, nres, true);
+        if constexpr (S.res_l2)
+            windows(reinterpret_cast<const h8*>(p.mfma_kt_frag) + (size_t)nres * (kKtOps * 64) + lane, nres, ng, false);
     }
     if constexpr (S.diag) dg.t_swp += __builtin_amdgcn_s_memtime() - tsw;
     return true;
@@ -299,6 +395,9 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
             atomicAdd(p.seg_counter + 14, dg.t_exact); // ... exact phase + Y rebuilds
             atomicAdd(p.seg_counter + 15, dg.t_swp);   // ... whole sweeps
             atomicAdd(p.seg_counter + 16, __builtin_amdgcn_s_memtime() - wl_c0);  // ... the wave's life
+            atomicAdd(p.seg_counter + 17, dg.t_issue);  // ... of the exact phase: waiting for an episode's first triangle
+            atomicAdd(p.seg_counter + 18, dg.t_pub);    // ... of the exact phase: the Y rebuilds
+            atomicAdd(p.seg_counter + 19, dg.claims);   // exact episodes
         }
 }
 

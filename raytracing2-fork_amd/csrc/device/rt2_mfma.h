@@ -57,6 +57,10 @@ struct MfmaSpec {
                              // the sweep)
     bool res_l2 = false;     // render_mfma_k5r: groups beyond the resident kResGroups are read from L2 (global loads
                              // per wave) after the resident ones: scenes of up to 256 groups
+    int exact_win = 1;       // render_mfma_k5r: groups per window (at most 64): the products of a window's groups run
+                             // back to back and one exact episode follows (rt2_k5_resident.h); 1 = per group
+    bool y_skip_last = false;  // render_mfma_k5r, exact_win = 1: no Y rebuild after the sweep's last group (windows
+                               // of more than one group never rebuild there)
 };
 
 // per-wave diagnostic counts (wave-uniform; MfmaSpec::diag)
@@ -73,7 +77,8 @@ struct MfmaDiag {
     // exact phase (with the Y rebuilds), the whole sweep
     unsigned long long t_wait = 0, t_filt = 0, t_exact = 0, t_swp = 0;
     unsigned long long unused1 = 0;
-    // sweep_kt_flow, of that: issuing the wave's tile shares, waiting for them to land; shares issued
+    // sweep_kt_flow, of that: issuing the wave's tile shares, waiting for them to land; shares issued.
+    // sweep_kt_res, of t_exact: waiting for an episode's first triangle to load, the Y rebuilds; exact episodes
     unsigned long long t_issue = 0, t_pub = 0, claims = 0;
 };
 

@@ -568,6 +568,14 @@ constexpr MfmaSpec kt_res(bool l2, bool fair, bool lane_w, int phase_prio = 0, b
     return MfmaSpec{.block = 1024, .waves = 4, .tail_lanes = 4, .diag = diag, .fair_prio = fair,
                     .phase_prio = phase_prio, .kt_lane_w = lane_w, .lean = true, .res_l2 = l2};
 }
+// ... with the exact phase once per window of `win` groups (rt2_k5_resident.h exact_window); skip_last: per group, but
+// no Y rebuild after the last group
+constexpr MfmaSpec kt_win(MfmaSpec x, int win, bool skip_last = false) {
+    x.exact_win = win;
+    x.y_skip_last = skip_last;
+    return x;
+}
+constexpr int kResWin = 38;  // the window of 353-356 (and the diagnostic 350): the whole resident sweep, then one episode
 constexpr int kResL2Groups = 256;  // render_mfma_k5r with res_l2: kResGroups groups resident, the rest from L2
 // records streamed through LDS tiles (rt2_k5_tiles.h): 19-group tiles, each ray's own W, issue priority by
 // finishing rank; 3 waves per SIMD
@@ -608,11 +616,11 @@ constexpr Variant kVariants[] = {
     // scenes of <= 256 groups (8,192 triangles; config B: 38, W: 57, K: 89): the resident kernel (rt2_k5_resident.h:
     // records in LDS for the whole launch, 38 groups, the rest read from L2) with the threshold in the K-slots
     // (DESIGN.md "The threshold in the K-slots"), each ray's own W, issue priority by phase; fair-share issue
-    // priority instead for rank slabs
-    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_res(false, false, true, 4)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
-    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_res(false, true, true)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
-    RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_res(true, false, true, 4)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
-    RT2_VARIANT(356, K_MFMA, render_mfma_k5r<kt_res(true, true, true)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw", kResL2Groups),
+    // priority instead for rank slabs; the exact phase once per window of kResWin groups
+    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 4), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
+    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, true, true), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
+    RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, true, 4), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
+    RT2_VARIANT(356, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, true, true), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw", kResL2Groups),
     // the default above 8,192 triangles: the LDS-tiled kernel (rt2_k5_tiles.h; 19-group tiles, fragments in
     // registers) with the threshold in the K-slots, each ray's own W in the bound
     RT2_VARIANT(380, K_MFMA, render_mfma_k5t<kt_tiles_flow4()>, 1024, "mfmat5/1024/kt4/tile19/coop0/w4/cmp/regs/perm/lw/flowp/lean"),
@@ -620,16 +628,29 @@ constexpr Variant kVariants[] = {
     // One knob away from a shipping matrix-filter kernel, plus one diagnostic build per template (DESIGN.md "Tried
     // and measured"; earlier generations are in git history).
     // the resident kernel with the wave's W in the bound (353-356 take each ray's own)
-    RT2_VARIANT(342, K_MFMA, render_mfma_k5r<kt_res(false, false, false)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean", kResGroups),
-    RT2_VARIANT(344, K_MFMA, render_mfma_k5r<kt_res(false, true, false)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean", kResGroups),
-    RT2_VARIANT(345, K_MFMA, render_mfma_k5r<kt_res(true, false, false)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean", kResL2Groups),
-    RT2_VARIANT(346, K_MFMA, render_mfma_k5r<kt_res(true, true, false)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean", kResL2Groups),
+    RT2_VARIANT(342, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, false), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean", kResGroups),
+    RT2_VARIANT(344, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, true, false), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean", kResGroups),
+    RT2_VARIANT(345, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, false), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean", kResL2Groups),
+    RT2_VARIANT(346, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, true, false), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean", kResL2Groups),
     // ... issue priority by phase 1 / 2 / 3 (353 takes 4) and without it; its diagnostic counters
-    RT2_VARIANT(387, K_MFMA, render_mfma_k5r<kt_res(false, false, true, 1)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp1", kResGroups),
-    RT2_VARIANT(388, K_MFMA, render_mfma_k5r<kt_res(false, false, true, 2)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp2", kResGroups),
-    RT2_VARIANT(389, K_MFMA, render_mfma_k5r<kt_res(false, false, true, 3)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp3", kResGroups),
-    RT2_VARIANT(391, K_MFMA, render_mfma_k5r<kt_res(false, false, true)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw", kResGroups),
-    RT2_VARIANT(350, K_MFMA, render_mfma_k5r<kt_res(false, false, true, 0, true)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw", kResGroups),
+    RT2_VARIANT(387, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 1), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp1", kResGroups),
+    RT2_VARIANT(388, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 2), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp2", kResGroups),
+    RT2_VARIANT(389, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 3), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp3", kResGroups),
+    RT2_VARIANT(391, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw", kResGroups),
+    RT2_VARIANT(350, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 0, true), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw", kResGroups),
+    // ... its per-group form with the same clocks
+    RT2_VARIANT(390, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 0, true), 1)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/xw1", kResGroups),
+    // the exact phase per window of W groups (353-356 take kResWin = 38): per group (xw1: the form before the window),
+    // per group without the Y rebuild after the last group (xw1s), W = 2, 4, 8, 19; the L2 continuation's and the
+    // fair-share kernel's per-group forms
+    RT2_VARIANT(392, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 4), 1)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/xw1", kResGroups),
+    RT2_VARIANT(393, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 4), 1, true)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/xw1s", kResGroups),
+    RT2_VARIANT(394, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 4), 2)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/xw2", kResGroups),
+    RT2_VARIANT(395, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 4), 4)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/xw4", kResGroups),
+    RT2_VARIANT(396, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 4), 8)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/xw8", kResGroups),
+    RT2_VARIANT(399, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 4), 19)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/xw19", kResGroups),
+    RT2_VARIANT(397, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, true, 4), 1)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4/xw1", kResL2Groups),
+    RT2_VARIANT(398, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, true, true), 1)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/xw1", kResGroups),
     // the tile stream at 3 waves per SIMD (380 takes 4 with the lean lane state): with its diagnostic clocks; without
     // flow_prio; with the lean lane state
     RT2_VARIANT(370, K_MFMA, render_mfma_k5t<kt_tiles_flow()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp"),

@@ -1,8 +1,9 @@
-"""Matrix-filter survivor statistics (diagnostic variants 350 / 368 = the
-resident kernel 391 and the tile stream 370 plus counters; experiment build,
-RT2_LIB=exp): per (wave, 32-triangle group) sweep, how often a pair passes the
-filter (the wave enters the exact phase) and how many (wave, triangle) exact
-tests follow."""
+"""Matrix-filter survivor statistics (diagnostic variants 350 / 390 / 368 = the
+resident kernel 391 with the default window and per group, and the tile stream
+370, plus counters; experiment build, RT2_LIB=exp): per (wave, 32-triangle
+group) sweep, how often a pair passes the filter (the wave enters the exact
+phase) and how many (wave, triangle) exact tests follow; for the resident
+kernel also its phase clocks."""
 import argparse
 import ctypes as C
 import json
@@ -26,6 +27,12 @@ u = rt2.offline_uniforms(a.width, a.height, spec.bounces, spec.rays, sd.num_tria
 scene = rt2.Scene(sd, 0)
 res = {"config": a.config, "width": a.width, "height": a.height, "triangles": sd.num_triangles}
 imgs = {}
+
+
+def name_of(v):
+    return rt2.lib().rt2_variant_name(v).decode()
+
+
 for v in [int(x) for x in a.variants.split(",")]:
     scene.set_variant(v)
     scene.render_host(u, 0, 1)  # warm
@@ -39,11 +46,27 @@ for v in [int(x) for x in a.variants.split(",")]:
     scene.stats(reset=True)
     imgs[v] = img
     groups, hot, exact = c[2], c[3], c[4]
-    res[rt2.lib().rt2_variant_name(v).decode()] = dict(
+    res[name_of(v)] = dict(
         ms=round(dt * 1e3, 1), segments=st.segments, wave_groups=groups,
         hot_group_rate=hot / max(groups, 1), exact_tests_per_group=exact / max(groups, 1),
         exact_tests_per_hot_group=exact / max(hot, 1),
         wave_triangle_exact_rate=exact / max(32 * groups, 1))
+    life = c[17]
+    if life and name_of(v).startswith(("mfmar/", "mfmarl2/")):
+        # the resident kernel's phase clocks (rt2_k5_resident.h): shares of the waves' life, and of the exact phase
+        # its three parts (the wait for an episode's first triangle, the tests, the Y rebuilds)
+        setup, filt, ex, load, reb, episodes = c[13], c[14], c[15], c[18], c[19], c[20]
+        sweeps = groups / max((sd.num_triangles + 31) // 32, 1)
+        res[name_of(v)].update(
+            life_share=dict(setup=round(setup / life, 4), products=round(filt / life, 4), exact=round(ex / life, 4),
+                            outside_sweep=round(1 - c[16] / life, 4)),
+            product_clocks_per_group=round(filt / max(groups, 1), 1),
+            exact_clocks_per_hot_group=round(ex / max(hot, 1), 1),
+            episodes_per_sweep=round(episodes / max(sweeps, 1), 2),
+            exact_clocks_per_episode=dict(first_load_wait=round(load / max(episodes, 1), 1),
+                                          tests=round((ex - load - reb) / max(episodes, 1), 1),
+                                          y_rebuild=round(reb / max(episodes, 1), 1),
+                                          whole=round(ex / max(episodes, 1), 1)))
 vs = list(imgs)
 res["bit_identical"] = all(bool((imgs[v] == imgs[vs[0]]).all()) for v in vs[1:])
 print(json.dumps(res, indent=1))
