@@ -45,6 +45,15 @@
 // only passes more pairs; those are decided by mt_pass3 / mt_exact against the
 // current bound, in index order, like every other survivor.  The price is
 // more tests (config B: 0.686 per (wave, group) against 0.634).
+//
+// A sweep's first window runs without the Y product (kt_group<false>): every
+// sweep starts with no distance bound, nothing rebuilds Y inside a window, so
+// Y there is the det > 0 test, which U, -V, X < 0 imply up to the thresholds
+// (rt2_mfma.h kt_group).  Leaving a term out of the conjunction only passes
+// more pairs.  The Y fragment is first built after that window, when groups
+// follow it; in a kernel whose first window is the whole scene (353, 354) it
+// never exists and the T1 records are not brought into LDS.
+// MfmaSpec::y_first keeps the Y product there (the A/B arms).
 #pragma once
 
 namespace {
@@ -167,13 +176,15 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
     h8 a0[2], y1[2];
     _Float16 tw16;
     kt_frags<S.kt_lane_w>(d, m, sc, a0, tw16);
-    kt_y(d, o, bestK, sc, tw16, y1);
+    constexpr bool per_group = S.exact_win == 1 && !S.y_skip_last && !S.diag;
+    // the window path's first window needs no Y fragment (MfmaSpec::y_first)
+    if constexpr (per_group || S.y_first) kt_y(d, o, bestK, sc, tw16, y1);
     stamp(dg.t_wait);
     const int ng = (p.n_tris + 31) >> 5, n_tris = p.n_tris;
     const int nres = S.res_l2 ? min(ng, kResGroups) : ng;
     cfloat* const tri = (cfloat*)p.tri;  // held across the sweep (not re-read from the kernel arguments per hot group)
     const h8* tb = rec + lane;
-    if constexpr (S.exact_win == 1 && !S.y_skip_last && !S.diag) {
+    if constexpr (per_group) {
         // one exact episode per hot group, the bound rebuilt after each
         for (int G = 0; G < nres; G++) {
             const h8 b0 = tb[0], b1 = tb[64], b2 = tb[128], b3 = tb[192];
@@ -197,37 +208,65 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
     } else {
         constexpr int W = S.exact_win;
         static_assert(W >= 1 && W <= 64, "a window's masks are the lanes of one VGPR");
-        // One loop of windows over the groups [G0, G1), records at tb (LDS
-        // or L2): the window's products back to back, each group's hot mask
-        // kept in lane (G - window start) of maskv, then one episode.
-        auto windows = [&](const h8* tb, int G0, int G1, bool resident) {
-            for (int Gw = G0; Gw < G1; Gw += W) {
-                const int cnt = W == 1 ? 1 : min(W, G1 - Gw);
-                int maskv = 0;
-                uint32_t any = 0;
-                for (int j = 0; j < cnt; j++) {
-                    const h8 b0 = tb[0], b1 = tb[64], b2 = tb[128], b3 = tb[192];
-                    tb += kKtOps * 64;
-                    const unsigned long long M = kt_group(a0, y1, b0, b1, b2, b3, upper);
-                    const uint32_t m32 = (uint32_t)(M | M >> 32);
-                    if constexpr (W > 1) maskv = lane == j ? (int)m32 : maskv;
-                    any |= m32;
-                }
-                if constexpr (S.diag) dg.groups += (unsigned long long)cnt;
-                if (resident) stamp(dg.t_filt);
-                if (any) {
-                    const bool more = Gw + cnt < ng || (W == 1 && !S.y_skip_last);
-                    if (resident) phase_prio<S>(1);
-                    exact_window<S>(any, maskv, Gw, cnt, more, n_tris, tri, o, d, best, bi, bestK, dg,
-                                    [&] { kt_y(d, o, bestK, sc, tw16, y1); });
-                    if (resident) phase_prio<S>(0);
-                }
-                if (resident) stamp(dg.t_exact);
+        // One window of the groups from Gw on (below G1), records at tb (LDS
+        // or L2; advanced): the window's products back to back, each group's
+        // hot mask kept in lane (G - window start) of maskv, then one episode.
+        // yp = false_type, the sweep's first window: no ray has a bound yet,
+        // so the products run without Y (kt_group<false>; the T1 record is not
+        // read) and y1 does not exist.  It is built after the window when
+        // groups follow, whether or not a bound improved and whether or not
+        // there was an episode: the next window's Y product reads it.
+        auto window = [&](auto yp, const h8*& tb, int Gw, int G1, bool resident) {
+            constexpr bool YP = decltype(yp)::value;
+            const int cnt = W == 1 ? 1 : min(W, G1 - Gw);
+            int maskv = 0;
+            uint32_t any = 0;
+            for (int j = 0; j < cnt; j++) {
+                const h8 b0 = tb[0], b1 = tb[64], b2 = tb[128];
+                h8 b3 = {};
+                if constexpr (YP) b3 = tb[192];
+                tb += kKtOps * 64;
+                const unsigned long long M = kt_group<YP>(a0, y1, b0, b1, b2, b3, upper);
+                const uint32_t m32 = (uint32_t)(M | M >> 32);
+                if constexpr (W > 1) maskv = lane == j ? (int)m32 : maskv;
+                any |= m32;
             }
+            if constexpr (S.diag) dg.groups += (unsigned long long)cnt;
+            if (resident) stamp(dg.t_filt);
+            if (any) {
+                const bool more = YP && (Gw + cnt < ng || (W == 1 && !S.y_skip_last));
+                if (resident) phase_prio<S>(1);
+                exact_window<S>(any, maskv, Gw, cnt, more, n_tris, tri, o, d, best, bi, bestK, dg,
+                                [&] { kt_y(d, o, bestK, sc, tw16, y1); });
+                if (resident) phase_prio<S>(0);
+            }
+            // a window of kResGroups is the whole sweep of a kernel without the L2 loop
+            if constexpr (!YP && (S.res_l2 || W < kResGroups))
+                if (Gw + cnt < ng) {
+                    [[maybe_unused]] unsigned long long ty = 0;
+                    if constexpr (S.diag) ty = __builtin_amdgcn_s_memtime();
+                    kt_y(d, o, bestK, sc, tw16, y1);
+                    if constexpr (S.diag) dg.t_pub += __builtin_amdgcn_s_memtime() - ty;
+                }
+            if (resident) stamp(dg.t_exact);
         };
-        windows(tb, 0, nres, true);
+        // The windows over the groups [G0, G1); yfirst = false_type: the first
+        // one, peeled, takes the form without Y.
+        auto windows = [&](auto yfirst, const h8* tb, int G0, int G1, bool resident) {
+            constexpr bool YF = decltype(yfirst)::value;
+            int Gw = G0;
+            if constexpr (!YF) {
+                if (Gw < G1) window(std::false_type{}, tb, Gw, G1, resident);
+                Gw += W;
+            }
+            // ... and a window of kResGroups is the whole resident stretch
+            if constexpr (YF || W < kResGroups)
+                for (; Gw < G1; Gw += W) window(std::true_type{}, tb, Gw, G1, resident);
+        };
+        windows(std::bool_constant<S.y_first>{}, tb, 0, nres, true);
         if constexpr (S.res_l2)
-            windows(reinterpret_cast<const h8*>(p.mfma_kt_frag) + (size_t)nres * (kKtOps * 64) + lane, nres, ng, false);
+            windows(std::true_type{}, reinterpret_cast<const h8*>(p.mfma_kt_frag) + (size_t)nres * (kKtOps * 64) + lane,
+                    nres, ng, false);
     }
     if constexpr (S.diag) dg.t_swp += __builtin_amdgcn_s_memtime() - tsw;
     return true;
@@ -248,7 +287,13 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
         const RenderParams& p = kargs<RenderParams>();
         const int ng = min((p.n_tris + 31) >> 5, kResGroups);
         const int lane = (int)lane_id(), wave = (int)(threadIdx.x >> 6);
-        for (int pc = wave; pc < 4 * ng; pc += NW) {
+        // The T1 records (every fourth piece) are read by the Y product only,
+        // which the resident groups never see when they are all one first
+        // window and nothing follows it: those pieces stay away (their LDS is
+        // never read; the layout is unchanged).
+        constexpr bool no_t1 = !S.y_first && S.exact_win >= kResGroups && !S.res_l2;
+        for (int i = wave; i < (no_t1 ? 3 : 4) * ng; i += NW) {
+            const int pc = no_t1 ? i + i / 3 : i;  // 4 G + op of U, -V, X's i = 3 G + op
             const h8* src = reinterpret_cast<const h8*>(p.mfma_kt_frag) + (size_t)pc * 64 + lane;  // [G][4 ops] contiguous
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)&rs.rec[pc * 64], 16, 0, 0);

@@ -61,6 +61,9 @@ struct MfmaSpec {
                              // back to back and one exact episode follows (rt2_k5_resident.h); 1 = per group
     bool y_skip_last = false;  // render_mfma_k5r, exact_win = 1: no Y rebuild after the sweep's last group (windows
                                // of more than one group never rebuild there)
+    bool y_first = false;  // render_mfma_k5r, window path: a sweep's first window runs the Y product too (no ray has a
+                           // bound there, so Y is the det > 0 test that U, -V, X imply); false: kt_group<false>, and
+                           // the Y fragment is first built after that window
 };
 
 // per-wave diagnostic counts (wave-uniform; MfmaSpec::diag)
@@ -536,6 +539,14 @@ __device__ __forceinline__ void kt_y(const f3& d, const f3& o, float bkv, const 
 // that each wave's own products run beside its own reduction VALU, at a
 // register peak of 48 product VGPRs: [U0 V0 X0] [AND0] [Y0 U1] [fold0] [V1 X1]
 // [AND1] [Y1] [fold1] (scheduling groups; one basic block per form).
+// Y = false: the form without the distance term, for a stretch of groups in
+// which no ray has a bound yet (y1, bt are not read).  Y is then -s Bmax det
+// minus its threshold, the det > 0 test, and U, -V, X < 0 already say 0 <
+// u_num + v_num < c det (DESIGN.md "No Y product without a bound"): the
+// conjunction without Y passes every pair the one with Y passes.  Three
+// products per block, the same 16 ANDs, and an OR chain of 8 three-input steps
+// over their results: [U0 V0 X0] [AND0] [U1] [or0] [V1 X1] [AND1] [or1].
+template <bool Y = true>
 __device__ __forceinline__ unsigned long long kt_group(const h8* a0, const h8* y1, const h8& bu, const h8& bv,
                                                        const h8& bx, const h8& bt, bool upper) {
     const f16v zero = {};
@@ -545,13 +556,46 @@ __device__ __forceinline__ unsigned long long kt_group(const h8* a0, const h8* y
         for (int i = 0; i < 16; i++)  // U & V & X (LUT index 4 S0 + 2 S1 + S2)
             t3[i] = __builtin_amdgcn_bitop3_b32(__float_as_int(U[i]), __float_as_int(V[i]), __float_as_int(X[i]), 0x80);
     };
-    auto fold = [&](const int* t3, const f16v& Y, int a) {
+    auto fold = [&](const int* t3, const f16v& Yt, int a) {
 #pragma unroll
         for (int i = 0; i < 16; i++)  // (t3 & Y) | a: one chain, no OR tree (which costs 0.5 more per pair)
-            a = __builtin_amdgcn_bitop3_b32(t3[i], __float_as_int(Y[i]), a, 0xEA);
+            a = __builtin_amdgcn_bitop3_b32(t3[i], __float_as_int(Yt[i]), a, 0xEA);
         return a;
     };
-    if (upper) {
+    auto orv = [](const int* t3, int a) {
+#pragma unroll
+        for (int i = 0; i < 8; i++)  // t3[2i] | t3[2i + 1] | a
+            a = __builtin_amdgcn_bitop3_b32(t3[2 * i], t3[2 * i + 1], a, 0xFE);
+        return a;
+    };
+    if constexpr (!Y) {
+        if (upper) {
+            int t0[16], t1[16];
+            const f16v U0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[0], bu, zero, 0, 0, 0);
+            const f16v V0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[0], bv, zero, 0, 0, 0);
+            const f16v X0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[0], bx, zero, 0, 0, 0);
+            andv(U0, V0, X0, t0);
+            const f16v U1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[1], bu, zero, 0, 0, 0);
+            acc = orv(t0, acc);
+            const f16v V1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[1], bv, zero, 0, 0, 0);
+            const f16v X1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[1], bx, zero, 0, 0, 0);
+            andv(U1, V1, X1, t1);
+            acc = orv(t1, acc);
+            __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);   // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);  // VALU
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 24, 0);
+        } else {
+            int t0[16];
+            const f16v U0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[0], bu, zero, 0, 0, 0);
+            const f16v V0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[0], bv, zero, 0, 0, 0);
+            const f16v X0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[0], bx, zero, 0, 0, 0);
+            andv(U0, V0, X0, t0);
+            acc = orv(t0, acc);
+        }
+    } else if (upper) {
         int t0[16], t1[16];
         const f16v U0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[0], bu, zero, 0, 0, 0);
         const f16v V0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[0], bv, zero, 0, 0, 0);

@@ -575,6 +575,13 @@ constexpr MfmaSpec kt_win(MfmaSpec x, int win, bool skip_last = false) {
     x.y_skip_last = skip_last;
     return x;
 }
+#ifdef RT2_EXPERIMENTS
+// ... with the Y product in the sweep's first window too (the A/B arms of MfmaSpec::y_first)
+constexpr MfmaSpec kt_yw(MfmaSpec x) {
+    x.y_first = true;
+    return x;
+}
+#endif
 constexpr int kResWin = 38;  // the window of 353-356 (and the diagnostic 350): the whole resident sweep, then one episode
 constexpr int kResL2Groups = 256;  // render_mfma_k5r with res_l2: kResGroups groups resident, the rest from L2
 // records streamed through LDS tiles (rt2_k5_tiles.h): 19-group tiles, each ray's own W, issue priority by
@@ -616,7 +623,8 @@ constexpr Variant kVariants[] = {
     // scenes of <= 256 groups (8,192 triangles; config B: 38, W: 57, K: 89): the resident kernel (rt2_k5_resident.h:
     // records in LDS for the whole launch, 38 groups, the rest read from L2) with the threshold in the K-slots
     // (DESIGN.md "The threshold in the K-slots"), each ray's own W, issue priority by phase; fair-share issue
-    // priority instead for rank slabs; the exact phase once per window of kResWin groups
+    // priority instead for rank slabs; the exact phase once per window of kResWin groups, the first window of a sweep
+    // without the Y product (DESIGN.md "No Y product without a bound")
     RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 4), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
     RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, true, true), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
     RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, true, 4), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
@@ -651,6 +659,10 @@ constexpr Variant kVariants[] = {
     RT2_VARIANT(399, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 4), 19)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/xw19", kResGroups),
     RT2_VARIANT(397, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, true, 4), 1)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4/xw1", kResL2Groups),
     RT2_VARIANT(398, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, true, true), 1)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/xw1", kResGroups),
+    // the Y product in a sweep's first window too (yw: the form before MfmaSpec::y_first; 353, 355 and 350 leave it out)
+    RT2_VARIANT(351, K_MFMA, render_mfma_k5r<kt_yw(kt_win(kt_res(false, false, true, 4), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/yw", kResGroups),
+    RT2_VARIANT(352, K_MFMA, render_mfma_k5r<kt_yw(kt_win(kt_res(true, false, true, 4), kResWin))>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4/yw", kResL2Groups),
+    RT2_VARIANT(357, K_MFMA, render_mfma_k5r<kt_yw(kt_win(kt_res(false, false, true, 0, true), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/yw", kResGroups),
     // the tile stream at 3 waves per SIMD (380 takes 4 with the lean lane state): with its diagnostic clocks; without
     // flow_prio; with the lean lane state
     RT2_VARIANT(370, K_MFMA, render_mfma_k5t<kt_tiles_flow()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp"),
