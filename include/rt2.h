@@ -208,6 +208,49 @@ int rt2_resolve_rgb8_reference(const uint32_t* accum8, int64_t n_pixels, uint32_
                                uint8_t* out_rgb);
 
 /* ------------------------------------------------------------------------
+ * (1a) Ray queries: the closest hit of a caller's rays
+ *
+ * hits[i] is the result of calculateRayCollision for ray i over the scene's
+ * triangles as uploaded (indices are those of the `tris` array given to
+ * rt2_scene_create), with rayTriangleIntersect (compute.glsl:302-340)
+ * verbatim and the scan started at best = bound_i:
+ *   - bound_i = tmax when 0 < tmax < 1e38f, otherwise 1e38f: zero, negative,
+ *     NaN and infinite tmax mean unbounded, so a zero-filled field gives the
+ *     reference behaviour.  A hit needs dst < bound_i (strict);
+ *   - on a miss tri = -1 and dst = bound_i;
+ *   - d need not be normalised; o and d may be any floats.  Non-finite
+ *     components give what the reference arithmetic gives, a miss, and do not
+ *     disturb the other rays of the call;
+ *   - RT2_TRAVERSAL_BRUTE: exact distance ties go to the lowest index.
+ *     RT2_TRAVERSAL_BVH: they resolve in the reference's visiting order
+ *     (calculateRayCollisionBVH, compute.glsl:410-460, started at best =
+ *     bound_i; needs `nodes` at rt2_scene_create).
+ * rt2_trace_rays reads d_rays and writes d_hits in DEVICE memory (n records
+ * each, d_rays aligned to 16 bytes and d_hits to 8, as any hipMalloc'ed array
+ * is) and is asynchronous on `stream` like rt2_render; it is ordered against
+ * the scene's other launches by the rule renders follow (a launch waits for
+ * the scene's previous one on any stream).  n == 0 returns 0 and launches
+ * nothing.  Bad arguments (a null scene, n < 0, a null or misaligned pointer
+ * with n > 0, unknown flag bits, BVH traversal on a scene without nodes)
+ * return < 0 before any device call.
+ * rt2_scene_stats counts a query as segments += n; tests and node_visits as
+ * for renders (brute force: segments * N; BVH: leaf tests and nodes popped).
+ * flags: RT2_TRACE_AUTO lets the launcher choose the kernel (the matrix-core
+ * filter for brute force wherever the scene is in its range);
+ * RT2_TRACE_SCALAR forces the one-thread-per-ray kernel for brute force, for
+ * A/B comparison and cross-checks.  Every choice gives the same bits.
+ * rt2_trace_rays_host is the blocking form over host arrays (no alignment
+ * requirement): its device staging buffers are kept by the scene between
+ * calls and freed by rt2_scene_destroy, like rt2_render_host's.
+ * ---------------------------------------------------------------------- */
+typedef struct rt2_ray { float o[3]; float tmax; float d[3]; float pad; } rt2_ray;   /* 32 B */
+typedef struct rt2_hit { float dst; int32_t tri; } rt2_hit;                          /*  8 B */
+enum { RT2_TRACE_AUTO = 0, RT2_TRACE_SCALAR = 1 };
+
+int rt2_trace_rays(rt2_scene* scene, const rt2_ray* d_rays, int64_t n, rt2_hit* d_hits, int flags, void* stream);
+int rt2_trace_rays_host(rt2_scene* scene, const rt2_ray* rays, int64_t n, rt2_hit* hits, int flags);
+
+/* ------------------------------------------------------------------------
  * (1b) Multi-GPU: row-tile shards + one RCCL gather
  *
  * The reference renders on one GPU and reads the framebuffer back with

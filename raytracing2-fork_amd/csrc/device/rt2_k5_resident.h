@@ -272,6 +272,34 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
     return true;
 }
 
+// The resident frame's preamble for trace_rays_k5r (rt2_query.h): every
+// resident group's 4 operands by LDS-DMA (1-KiB pieces, coalesced 16 B per
+// lane, no VGPRs), dealt round-robin over the workgroup's waves; then one
+// barrier: every wave's pieces have landed.  render_mfma_k5r below keeps the
+// same text inline: calling this function there gives the render kernels
+// other register assignments and another schedule of the preamble than the
+// code DESIGN.md's measurements are of.
+template <MfmaSpec S>
+__device__ __forceinline__ void res_load_records(K5Resident& rs) {
+    constexpr int NW = S.block / 64;
+    const RenderParams& p = kargs<RenderParams>();
+    const int ng = min((p.n_tris + 31) >> 5, kResGroups);
+    const int lane = (int)lane_id(), wave = (int)(threadIdx.x >> 6);
+    // The T1 records (every fourth piece) are read by the Y product only,
+    // which the resident groups never see when they are all one first
+    // window and nothing follows it: those pieces stay away (their LDS is
+    // never read; the layout is unchanged).
+    constexpr bool no_t1 = !S.y_first && S.exact_win >= kResGroups && !S.res_l2;
+    for (int i = wave; i < (no_t1 ? 3 : 4) * ng; i += NW) {
+        const int pc = no_t1 ? i + i / 3 : i;  // 4 G + op of U, -V, X's i = 3 G + op
+        const h8* src = reinterpret_cast<const h8*>(p.mfma_kt_frag) + (size_t)pc * 64 + lane;  // [G][4 ops] contiguous
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                         (__attribute__((address_space(3))) void*)&rs.rec[pc * 64], 16, 0, 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+
 // render_mfma's segment loop with free-running waves (no barrier after the
 // records have landed) around sweep_kt_res; the path state stays in
 // registers.  The launcher takes it only for scenes of at most kResGroups

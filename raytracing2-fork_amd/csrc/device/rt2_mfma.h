@@ -752,8 +752,9 @@ __device__ __forceinline__ bool sweep_k16(const RenderParams& p, MfmaK16LaneLds&
 // Closest hit of every ray of `act` (lane j's o, d), one ray at a time by the
 // whole wave (coop_closest: the sequential strict-< scan's result); lane j
 // receives its own ray's (best, bi), lanes outside `act` keep theirs.
+// `bound` (nullable): lane j's starting bound (coop_closest's `bound`).
 __device__ __forceinline__ void coop_each(unsigned long long act, const f3& o, const f3& d, const RenderParams& p,
-                                          float& best, int& bi) {
+                                          float& best, int& bi, const float* bound = nullptr) {
     while (act) {
         const int j = __builtin_ctzll(act);
         act &= act - 1;
@@ -761,7 +762,7 @@ __device__ __forceinline__ void coop_each(unsigned long long act, const f3& o, c
         const f3 dj = mk(__shfl(d.x, j), __shfl(d.y, j), __shfl(d.z, j));
         float b;
         int bidx;
-        coop_closest(oj, dj, p.tri, p.n_tris, b, bidx);
+        coop_closest(oj, dj, p.tri, p.n_tris, b, bidx, bound ? __shfl(*bound, j) : 1e38f);
         if ((int)lane_id() == j) {
             best = b;
             bi = bidx;

@@ -43,6 +43,7 @@ using namespace rt2d;
 #include "rt2_assist.h"
 #include "rt2_bvh.h"
 #include "rt2_misc_kernels.h"
+#include "rt2_query.h"
 
 /* =========================================================================
  * C-ABI, device half
@@ -119,6 +120,11 @@ struct rt2_scene {
     uint4* d_host_acc8 = nullptr;   // 8-bit path sums
     uint8_t* d_host_rgb8 = nullptr; // 8-bit path result (3 B per pixel)
     size_t host_cap = 0;            // pixels the four buffers hold
+    // rt2_trace_rays_host: staging buffers, kept like the above
+    rt2_ray* d_query_rays = nullptr;
+    rt2_hit* d_query_hits = nullptr;
+    size_t query_cap = 0;           // rays the two buffers hold
+    int query_arm = 0;                // experiment build: A/B arm of the resident query kernel
     unsigned long long* d_region_ctr = nullptr;  // 8 item-region counters, 128 B apart
     unsigned long long* wave_log = nullptr;  // diagnostic wave timeline (rt2_scene_set_wave_log)
     uint32_t wave_log_n = 0;
@@ -497,6 +503,8 @@ extern "C" void rt2_scene_destroy(rt2_scene* s) {
     (void)hipFree(s->d_host_res);
     (void)hipFree(s->d_host_acc8);
     (void)hipFree(s->d_host_rgb8);
+    (void)hipFree(s->d_query_rays);
+    (void)hipFree(s->d_query_hits);
     (void)hipFree(s->d_region_ctr);
     if (s->host_stream) (void)hipStreamDestroy(s->host_stream);
     delete s;
@@ -1173,6 +1181,144 @@ extern "C" int rt2_render_host(rt2_scene* s, const rt2_uniforms* u, uint32_t fra
         HIPCHECK(hipMemcpyAsync(out_rgb8, s->d_host_rgb8, n * 3, hipMemcpyDeviceToHost, st));
     }
     HIPCHECK(hipStreamSynchronize(st));  // only this render's stream, not the device
+    return 0;
+}
+
+/* -------------------------------------------------------------------------
+ * Ray queries (rt2_query.h)
+ * ----------------------------------------------------------------------- */
+namespace {
+// trace_rays_k5r with the arithmetic of 353 (every group resident) and of 355
+// (38 groups resident, the rest read from L2: no structural limit at 256
+// groups, so it serves every larger scene in the filter's range too)
+constexpr MfmaSpec kQueryRes = kt_win(kt_res(false, false, true, 4), kResWin);
+constexpr MfmaSpec kQueryResL2 = kt_win(kt_res(true, false, true, 4), kResWin);
+#ifdef RT2_EXPERIMENTS
+// A/B arms of the resident query kernel (rt2_scene_set_query_arm): 1 = its diagnostic counters and clocks (the
+// render's 350), 2 = the Y product in the first window too, which a caller's tmax can prune with (the render's 351)
+constexpr MfmaSpec kQueryResDiag = kt_win(kt_res(false, false, true, 0, true), kResWin);
+constexpr MfmaSpec kQueryResYw = kt_yw(kQueryRes);
+#endif
+constexpr int kQueryBlock = 256;                  // trace_rays_scalar
+constexpr long long kQuerySlice = 1ll << 30;      // rays per trace_rays_scalar launch (its grid: 2^22 blocks)
+// what rt2_scene_diag reports as the variant last launched after a query (renders: a kVariants id, or -1)
+enum : int { Q_RES = -2, Q_RES_L2 = -3, Q_SCALAR = -4, Q_BVH = -5 };
+}  // namespace
+
+#ifdef RT2_EXPERIMENTS
+// Not in rt2.h (experiment build): 0 = the product kernel, 1 / 2 = kQueryResDiag / kQueryResYw for scenes of at most
+// kResGroups groups.
+extern "C" int rt2_scene_set_query_arm(rt2_scene* s, int arm) {
+    if (!s || arm < 0 || arm > 2) return -1;
+    s->query_arm = arm;
+    return 0;
+}
+#endif
+
+extern "C" int rt2_trace_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, rt2_hit* d_hits, int flags,
+                              void* stream) {
+    if (!s || n < 0 || (n > 0 && (!d_rays || !d_hits)) || (flags & ~RT2_TRACE_SCALAR) ||
+        (reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 7)) {
+        rt2h::set_error("rt2_trace_rays: bad argument (a scene, n >= 0, rays aligned to 16 B and hits to 8 B, flags "
+                        "0 or RT2_TRACE_SCALAR)");
+        return -1;
+    }
+    if (n == 0) return 0;
+    const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
+    if (bvh && s->n_nodes == 0) {
+        rt2h::set_error("rt2_trace_rays: bad argument (BVH traversal needs the node array)");
+        return -1;
+    }
+    HIPCHECK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.tri = s->d_tri;
+    p.n_tris = s->n_tris;
+    p.mfma_A = s->mfma_A;
+    p.mfma_kt_frag = s->d_mfma_kt;
+    p.nodes = s->d_nodes;
+    p.stack_slots = s->bvh_depth + 2;
+    p.item_counter = s->d_counters;
+    p.seg_counter = s->d_counters + 1;
+    QueryParams q{d_rays, d_hits, (long long)n};
+    // RT2_TRACE_AUTO: the matrix kernel at every ray count.  On config B it beat the scalar kernel in every round
+    // from 2^22 rays down to one 64-ray chunk (36 against 142 us; profiles/trace_rays_ab.json), and below 64 rays
+    // both kernels are one wave whose time no longer falls: no small-batch threshold is needed.
+    const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
+    // a query shares the scene's counters with its renders: the same order
+    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
+    if (matrix) {
+        // one 16-wave workgroup per CU, and no more workgroups than have 1,024 rays each:
+        // every one of them brings the resident records into its LDS
+        const unsigned blocks = (unsigned)std::min<long long>(s->num_cus, (n + 1023) / 1024);
+        const bool resident = (s->n_tris + 31) / 32 <= kResGroups;
+#ifdef RT2_EXPERIMENTS
+        if (resident && s->query_arm == 1)
+            hipLaunchKernelGGL(trace_rays_k5r<kQueryResDiag>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
+        else if (resident && s->query_arm == 2)
+            hipLaunchKernelGGL(trace_rays_k5r<kQueryResYw>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
+        else
+#endif
+        if (resident)
+            hipLaunchKernelGGL(trace_rays_k5r<kQueryRes>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
+        else
+            hipLaunchKernelGGL(trace_rays_k5r<kQueryResL2>, dim3(blocks), dim3(kQueryResL2.block), 0, st, p, q);
+        HIPCHECK(hipGetLastError());
+        s->last_kind = K_MFMA;
+        s->last_variant = resident ? Q_RES : Q_RES_L2;
+    } else {
+        for (long long i0 = 0; i0 < (long long)n; i0 += kQuerySlice) {
+            q.rays = d_rays + i0;
+            q.hits = d_hits + i0;
+            q.n = std::min<long long>(kQuerySlice, (long long)n - i0);
+            const unsigned blocks = (unsigned)((q.n + kQueryBlock - 1) / kQueryBlock);
+            if (bvh)
+                hipLaunchKernelGGL((trace_rays_scalar<kQueryBlock, true>), dim3(blocks), dim3(kQueryBlock),
+                                   (size_t)p.stack_slots * kQueryBlock * sizeof(int), st, p, q);
+            else
+                hipLaunchKernelGGL((trace_rays_scalar<kQueryBlock, false>), dim3(blocks), dim3(kQueryBlock), 0, st, p,
+                                   q);
+            HIPCHECK(hipGetLastError());
+        }
+        s->last_kind = bvh ? K_BVH : K_SMEM;
+        s->last_variant = bvh ? Q_BVH : Q_SCALAR;
+    }
+    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(s->last_launch, st));
+    s->last_launch_valid = true;
+    s->tests_per_seg = (unsigned long long)s->n_tris;
+    return 0;
+}
+
+extern "C" int rt2_trace_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n, rt2_hit* hits, int flags) {
+    if (!s || n < 0 || (n > 0 && (!rays || !hits)) || (flags & ~RT2_TRACE_SCALAR)) {
+        rt2h::set_error("rt2_trace_rays_host: bad argument (a scene, n >= 0, flags 0 or RT2_TRACE_SCALAR)");
+        return -1;
+    }
+    if (n == 0) return 0;
+    if (s->traversal == RT2_TRAVERSAL_BVH && s->n_nodes == 0) {
+        rt2h::set_error("rt2_trace_rays_host: bad argument (BVH traversal needs the node array)");
+        return -1;
+    }
+    HIPCHECK(hipSetDevice(s->device));
+    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    hipStream_t st = s->host_stream;
+    if ((size_t)n > s->query_cap) {
+        HIPCHECK(hipStreamSynchronize(st));
+        (void)hipFree(s->d_query_rays);
+        (void)hipFree(s->d_query_hits);
+        s->d_query_rays = nullptr;
+        s->d_query_hits = nullptr;
+        s->query_cap = 0;
+        HIPCHECK(hipMalloc(&s->d_query_rays, (size_t)n * sizeof(rt2_ray)));
+        HIPCHECK(hipMalloc(&s->d_query_hits, (size_t)n * sizeof(rt2_hit)));
+        s->query_cap = (size_t)n;
+    }
+    HIPCHECK(hipMemcpyAsync(s->d_query_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
+    if (rt2_trace_rays(s, s->d_query_rays, n, s->d_query_hits, flags, st) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(hits, s->d_query_hits, (size_t)n * sizeof(rt2_hit), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
     return 0;
 }
 

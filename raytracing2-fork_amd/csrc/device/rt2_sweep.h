@@ -360,11 +360,12 @@ __device__ __forceinline__ bool plk_lane_ok(const f3& o, const f3& d) {
 // running best) and the wave reduces (dst, index) lexicographically.  The
 // result equals the sequential strict-< scan: the minimum distance, and among
 // exact ties the lowest index.  Triangle records are read from `tris`
-// (LDS or global) with per-lane addresses.
+// (LDS or global) with per-lane addresses.  `bound`: where the scan starts
+// (a ray query's tmax; a miss returns it).
 __device__ __forceinline__ void coop_closest(const f3& o, const f3& d, const float4* tris, int n, float& best_out,
-                                             int& bi_out) {
+                                             int& bi_out, float bound = 1e38f) {
     const int lane = (int)lane_id();
-    float best = 1e38f, bestK = 1e38f * 1.0009765625f;
+    float best = bound, bestK = bound * 1.0009765625f;
     int bi = -1;
     for (int i = lane; i < n; i += 64) {
         const float4* t = tris + 3 * i;

@@ -153,6 +153,12 @@ MAT_DTYPE = np.dtype([("color", "<f4", 4), ("specularColor", "<f4", 4), ("emissi
 NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("pad0", "<f4"), ("bmax", "<f4", 3), ("pad1", "<f4"),
                        ("triangleIndex", "<i4"), ("triangleCount", "<i4"), ("childIndex", "<i4"), ("pad", "<i4")])
 assert TRI_DTYPE.itemsize == 80 and MAT_DTYPE.itemsize == 96 and NODE_DTYPE.itemsize == 48
+# rt2_ray / rt2_hit (ray queries); tmax: 0 (or anything outside (0, 1e38)) = unbounded
+RAY_DTYPE = np.dtype([("o", "<f4", 3), ("tmax", "<f4"), ("d", "<f4", 3), ("pad", "<f4")])
+HIT_DTYPE = np.dtype([("dst", "<f4"), ("tri", "<i4")])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 8
+TRACE_AUTO, TRACE_SCALAR = 0, 1  # RT2_TRACE_AUTO, RT2_TRACE_SCALAR
+QUERY_RES, QUERY_RES_L2, QUERY_SCALAR, QUERY_BVH = -2, -3, -4, -5  # Scene.last_kernel after a query
 
 # Every symbol include/rt2.h declares (tests check the library exports them all).
 EXPORTED = [
@@ -169,7 +175,7 @@ EXPORTED = [
     "rt2_uniforms_offline", "rt2_write_png", "rt2_image_load", "rt2_image_free", "rt2_sd_texture",
     "rt2_scene_set_textures", "rt2_comm_unique_id", "rt2_comm_init", "rt2_comm_wrap", "rt2_comm_destroy",
     "rt2_comm_size", "rt2_comm_check", "rt2_gather_slabs", "rt2_unshard_slabs", "rt2_render_host_gather",
-    "rt2_comm_wait",
+    "rt2_comm_wait", "rt2_trace_rays", "rt2_trace_rays_host",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -209,6 +215,8 @@ def lib() -> C.CDLL:
         "rt2_shard_row": (I32, [I32, Shard]),
         "rt2_render": (C.c_int, [P, C.POINTER(Uniforms), U32, U32, Shard, P, P, P]),
         "rt2_render_host": (C.c_int, [P, C.POINTER(Uniforms), U32, U32, Shard, P, P]),
+        "rt2_trace_rays": (C.c_int, [P, P, I64, P, C.c_int, P]),
+        "rt2_trace_rays_host": (C.c_int, [P, P, I64, P, C.c_int]),
         "rt2_resolve_rgba32f": (C.c_int, [P, I64, U32, P, P]),
         "rt2_resolve_rgb8_reference": (C.c_int, [P, I64, U32, P]),
         "rt2_scene_stats": (C.c_int, [P, C.POINTER(Stats), C.c_int]),
@@ -586,6 +594,39 @@ class Scene:
         if not is_root:
             return None
         return (out, out8) if rgb8 else out
+
+    def trace_rays(self, origins, directions, tmax=None, flags: int = 0):
+        """Closest hit of n rays (rt2_trace_rays_host, blocking): origins and
+        directions (n, 3), tmax None (unbounded), a scalar or (n,).  Returns
+        (dst float32[n], tri int32[n]); a miss has tri = -1 and dst = the ray's
+        bound.  Indices are those of the triangle array the scene was made of."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise RT2Error(f"trace_rays: {len(o)} origins for {len(d)} directions")
+        rays = np.zeros(len(o), dtype=RAY_DTYPE)
+        rays["o"], rays["d"] = o, d
+        if tmax is not None:
+            rays["tmax"] = np.asarray(tmax, dtype=np.float32)
+        hits = np.zeros(len(o), dtype=HIT_DTYPE)
+        _check(lib().rt2_trace_rays_host(self._p, rays.ctypes.data, len(rays), hits.ctypes.data, int(flags)),
+               "rt2_trace_rays_host")
+        return hits["dst"].copy(), hits["tri"].copy()
+
+    def trace_rays_device(self, rays_ptr: int, n: int, hits_ptr: int, flags: int = 0, stream: int = 0) -> None:
+        """Asynchronous query over device arrays of n rt2_ray / rt2_hit records (rt2_trace_rays)."""
+        _check(lib().rt2_trace_rays(self._p, C.c_void_p(rays_ptr) if rays_ptr else None, int(n),
+                                    C.c_void_p(hits_ptr) if hits_ptr else None, int(flags),
+                                    C.c_void_p(stream) if stream else None), "rt2_trace_rays")
+
+    def last_kernel(self) -> int:
+        """What the scene launched last (rt2_scene_diag): a render's variant id (-1: the traceBasic preview), or
+        after a query QUERY_RES (trace_rays_k5r, every group resident), QUERY_RES_L2 (its L2 continuation),
+        QUERY_SCALAR or QUERY_BVH (trace_rays_scalar)."""
+        c, v = (C.c_ulonglong * 8)(), C.c_int(-1)
+        if lib().rt2_scene_diag(self._p, c, C.byref(v)) != 0:
+            raise RT2Error("rt2_scene_diag failed")
+        return v.value
 
     def export(self, what: int, dtype) -> np.ndarray:
         """A derived device array of the scene (rt2_scene_export, test hook): 0 =

@@ -14,6 +14,8 @@
 #                    ("default" = --full: the headline and every leg beside it)
 #   STATS="B C E"    rocprofv3 --kernel-trace --stats of a bench run per config
 #   PMC="B C E"      PMC passes (scripts/profile_pmc.sh) of the bench's render kernel per config
+#   TRACE_AB=<rounds>  ray-query A/B, matrix against scalar kernel (scripts/trace_rays_ab.py): rewrites
+#                    profiles/trace_rays_ab.json and prints its summary; TRACE_AB_OUT=<file> writes there instead
 #   TAG=<name>       suffix of the output files
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
@@ -50,6 +52,11 @@ for spec in ${SHARD}; do
     2> "gpurun_out/shard_${T}_${cfg}.err" || { echo "shard probe $spec failed"; tail -20 "gpurun_out/shard_${T}_${cfg}.err"; exit 1; }
   echo "shard probe $cfg ok"
 done
+if [ -n "${TRACE_AB}" ]; then
+  timeout -k 10 900 python -u scripts/trace_rays_ab.py --rounds "${TRACE_AB}" ${TRACE_AB_OUT:+--out "$TRACE_AB_OUT"} \
+    || { echo "ray-query A/B failed"; exit 1; }
+  echo "ray-query A/B ok"
+fi
 if [ -n "${BENCH}" ]; then
   bargs="${BENCH}"; [ "${BENCH}" = default ] && bargs="--full"
   timeout -k 10 900 python bench.py ${bargs} > "gpurun_out/bench_$T.json" 2> "gpurun_out/bench_$T.err" \
