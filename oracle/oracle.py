@@ -60,44 +60,75 @@ def default_threads() -> int:
     return max(1, n)
 
 
-def build() -> None:
-    subprocess.run(["make", "-C", HERE, "liboracle.so"], check=True, stdout=subprocess.DEVNULL)
+def build(force: bool = False) -> None:
+    """make liboracle.so; force: rebuild whatever the file dates say."""
+    subprocess.run(["make", "-C", HERE] + (["-B"] if force else []) + ["liboracle.so"], check=True,
+                   stdout=subprocess.DEVNULL)
+
+
+def _load() -> C.CDLL:
+    """liboracle.so, rebuilt first when it is missing or predates the newest
+    entry point (a library left by an earlier checkout: the callers that build
+    it only look whether the file exists)."""
+    if not os.path.exists(LIB):
+        build()
+    L = C.CDLL(LIB)
+    if not hasattr(L, "oracle_closest_hits"):
+        import _ctypes
+        handle = L._handle
+        del L
+        _ctypes.dlclose(handle)  # unmapped before the file is replaced and loaded again
+        build(force=True)
+        L = C.CDLL(LIB)
+        if not hasattr(L, "oracle_closest_hits"):
+            raise RuntimeError(f"{LIB} lacks oracle_closest_hits after a rebuild")
+    return L
+
+
+def load(path: str) -> C.CDLL:
+    """A build of the oracle at `path` with its entry points declared (the
+    tests load mutated builds beside liboracle.so)."""
+    return _declare(C.CDLL(path))
 
 
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB):
-            build()
-        L = C.CDLL(LIB)
-        P = C.c_void_p
-        L.oracle_render.restype = C.c_int
-        L.oracle_render.argtypes = [P, C.c_int32, P, C.c_int32, P, C.c_int32, P, C.c_uint32, C.c_uint32, P,
-                                    C.c_int32, C.c_int32, C.c_int32, P, P, P, P]
-        L.oracle_render_pixels.restype = C.c_int
-        L.oracle_render_pixels.argtypes = [P, C.c_int32, P, C.c_int32, P, C.c_int32, P, C.c_uint32, C.c_uint32, P,
-                                           C.c_int64, C.c_int32, C.c_int32, P, P, P, P]
-        L.oracle_set_textures.restype = C.c_int
-        L.oracle_set_textures.argtypes = [P, P, C.c_int32]
-        L.oracle_pcg_next.restype = C.c_uint32
-        L.oracle_pcg_next.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
-        L.oracle_ray_triangle.restype = C.c_int
-        L.oracle_ray_triangle.argtypes = [P, P, P, P]
-        L.oracle_sky.restype = None
-        L.oracle_sky.argtypes = [P, P]
-        L.oracle_tonemap_srgb.restype = C.c_float
-        L.oracle_tonemap_srgb.argtypes = [C.c_float]
-        L.oracle_pinned.restype = C.c_float
-        L.oracle_pinned.argtypes = [C.c_int, C.c_float]
-        _lib = L
+        _lib = _declare(_load())
     return _lib
+
+
+def _declare(L: C.CDLL) -> C.CDLL:
+    P = C.c_void_p
+    L.oracle_render.restype = C.c_int
+    L.oracle_render.argtypes = [P, C.c_int32, P, C.c_int32, P, C.c_int32, P, C.c_uint32, C.c_uint32, P,
+                                C.c_int32, C.c_int32, C.c_int32, P, P, P, P]
+    L.oracle_render_pixels.restype = C.c_int
+    L.oracle_render_pixels.argtypes = [P, C.c_int32, P, C.c_int32, P, C.c_int32, P, C.c_uint32, C.c_uint32, P,
+                                       C.c_int64, C.c_int32, C.c_int32, P, P, P, P]
+    L.oracle_closest_hits.restype = C.c_int
+    L.oracle_closest_hits.argtypes = [P, C.c_int32, P, C.c_int32, P, P, P, C.c_int64, C.c_int32, P, P, P, P]
+    L.oracle_set_textures.restype = C.c_int
+    L.oracle_set_textures.argtypes = [P, P, C.c_int32]
+    L.oracle_pcg_next.restype = C.c_uint32
+    L.oracle_pcg_next.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    L.oracle_ray_triangle.restype = C.c_int
+    L.oracle_ray_triangle.argtypes = [P, P, P, P]
+    L.oracle_sky.restype = None
+    L.oracle_sky.argtypes = [P, P]
+    L.oracle_tonemap_srgb.restype = C.c_float
+    L.oracle_tonemap_srgb.argtypes = [C.c_float]
+    L.oracle_pinned.restype = C.c_float
+    L.oracle_pinned.argtypes = [C.c_int, C.c_float]
+    return L
 
 
 def render(triangles: np.ndarray, materials: np.ndarray, uniforms, rows, frame_begin: int = 0,
            frame_count: int = 1, mode: str = "brute", nodes: np.ndarray | None = None, threads: int | None = None,
-           with_acc8: bool = False):
+           with_acc8: bool = False, library: C.CDLL | None = None):
     """Renders the listed image rows.  Returns (accum[nrows, W, 4] = per-pixel SUM over
-    frames, acc8 or None, segments, tests)."""
+    frames, acc8 or None, segments, tests).  library: another build of the
+    oracle (load()) instead of liboracle.so."""
     tri = np.ascontiguousarray(triangles)
     mat = np.ascontiguousarray(materials)
     assert tri.dtype.itemsize == 80 and mat.dtype.itemsize == 96
@@ -109,11 +140,12 @@ def render(triangles: np.ndarray, materials: np.ndarray, uniforms, rows, frame_b
     tests = C.c_uint64(0)
     nd = None if nodes is None else np.ascontiguousarray(nodes)
     m = {"brute": 0, "bvh": 1}[mode]
-    rc = lib().oracle_render(tri.ctypes.data, len(tri), mat.ctypes.data, len(mat),
-                             None if nd is None else nd.ctypes.data, 0 if nd is None else len(nd),
-                             C.addressof(uniforms), frame_begin, frame_count, rows.ctypes.data, len(rows), m,
-                             threads or default_threads(), acc.ctypes.data,
-                             None if acc8 is None else acc8.ctypes.data, C.byref(segs), C.byref(tests))
+    L = library or lib()
+    rc = L.oracle_render(tri.ctypes.data, len(tri), mat.ctypes.data, len(mat),
+                         None if nd is None else nd.ctypes.data, 0 if nd is None else len(nd),
+                         C.addressof(uniforms), frame_begin, frame_count, rows.ctypes.data, len(rows), m,
+                         threads or default_threads(), acc.ctypes.data,
+                         None if acc8 is None else acc8.ctypes.data, C.byref(segs), C.byref(tests))
     if rc != 0:
         raise RuntimeError(f"oracle_render failed: {rc}")
     return acc, acc8, segs.value, tests.value
@@ -143,6 +175,37 @@ def render_pixels(triangles: np.ndarray, materials: np.ndarray, uniforms, xs, ys
     if rc != 0:
         raise RuntimeError(f"oracle_render_pixels failed: {rc}")
     return acc, acc8, segs.value, tests.value
+
+
+def closest_hits(triangles: np.ndarray, origins, directions, bound=None, mode: str = "brute",
+                 nodes: np.ndarray | None = None, library: C.CDLL | None = None):
+    """The closest hit of each ray (origins, directions: (n, 3) float32), the
+    scan started at bound[i] (None: 1e38 everywhere; a scalar or (n,)): the
+    array scan ("brute") or the BVH walk over `nodes` ("bvh").  Returns (dst
+    float32[n], tri int32[n], tests uint64[n], visits uint64[n]); a miss has
+    tri = -1 and dst = its bound.  library: as for render()."""
+    tri = np.ascontiguousarray(triangles)
+    assert tri.dtype.itemsize == 80
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    n = len(o)
+    assert len(d) == n
+    b = np.full(n, 1e38, np.float32) if bound is None else \
+        np.ascontiguousarray(np.broadcast_to(np.asarray(bound, np.float32), (n,)))
+    nd = None if nodes is None else np.ascontiguousarray(nodes)
+    assert nd is None or nd.dtype.itemsize == 48
+    dst = np.empty(n, np.float32)
+    idx = np.empty(n, np.int32)
+    tests = np.zeros(n, np.uint64)
+    visits = np.zeros(n, np.uint64)
+    L = library or lib()
+    rc = L.oracle_closest_hits(tri.ctypes.data, len(tri), None if nd is None else nd.ctypes.data,
+                               0 if nd is None else len(nd), o.ctypes.data, d.ctypes.data, b.ctypes.data, n,
+                               {"brute": 0, "bvh": 1}[mode], dst.ctypes.data, idx.ctypes.data, tests.ctypes.data,
+                               visits.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle_closest_hits failed: {rc}")
+    return dst, idx, tests, visits
 
 
 _tex_keep = None

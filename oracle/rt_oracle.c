@@ -204,11 +204,13 @@ typedef struct {
 } ctx_t;
 
 /* Closest hit.  Brute force: every triangle in array order, `dst < best`
- * (compute.glsl:432-434).  BVH: compute.glsl:410-460. */
-static hit_t closest(const ctx_t* c, v3 o, v3 d, uint64_t* tests) {
+ * (compute.glsl:432-434).  BVH: compute.glsl:410-460.  The scan starts at
+ * r.dst = bound (the shader's 1e38; a ray query's own bound); *visits counts
+ * the interior nodes popped. */
+static hit_t closest_from(const ctx_t* c, v3 o, v3 d, float bound, uint64_t* tests, uint64_t* visits) {
     hit_t r;
     r.didHit = 0;
-    r.dst = 1e38f;
+    r.dst = bound;
     r.tri = -1;
     if (c->mode == 0) {
         for (int i = 0; i < c->n_tris; i++) {
@@ -239,6 +241,7 @@ static hit_t closest(const ctx_t* c, v3 o, v3 d, uint64_t* tests) {
                 }
             }
         } else {
+            *visits += 1;
             int ia = node->childIndex, ib = node->childIndex + 1;
             float dstA = ray_bounds(o, d, &c->nodes[ia]);
             float dstB = ray_bounds(o, d, &c->nodes[ib]);
@@ -252,6 +255,11 @@ static hit_t closest(const ctx_t* c, v3 o, v3 d, uint64_t* tests) {
         }
     }
     return r;
+}
+
+static hit_t closest(const ctx_t* c, v3 o, v3 d, uint64_t* tests) {
+    uint64_t visits = 0;
+    return closest_from(c, o, d, 1e38f, tests, &visits);
 }
 
 /* ---- textures (getTriangleTextureColor, compute.glsl:342-368) ------------
@@ -669,6 +677,29 @@ int oracle_render(const oracle_triangle* tris, int32_t n_tris, const oracle_mate
                                   W * n_rows, mode, threads, out_accum, out_acc8, out_segments, out_tests);
     free(px);
     return rc;
+}
+
+/* Closest hit per ray: closest_from() started at r.dst = bound[i], for n rays
+ * (o, d: n * 3 floats).  out_dst / out_tri: the hit (a miss keeps dst = the
+ * bound and tri = -1); out_tests / out_visits (nullable): the ray's leaf
+ * triangle tests and interior nodes popped (mode 0: n_tris and 0). */
+int oracle_closest_hits(const oracle_triangle* tris, int32_t n_tris, const oracle_node* nodes, int32_t n_nodes,
+                        const float* o, const float* d, const float* bound, int64_t n, int32_t mode, float* out_dst,
+                        int32_t* out_tri, uint64_t* out_tests, uint64_t* out_visits) {
+    if (n < 0 || n_tris < 0 || (n_tris > 0 && !tris) || (mode != 0 && mode != 1)) return -1;
+    if (n > 0 && (!o || !d || !bound || !out_dst || !out_tri)) return -1;
+    if (mode == 1 && (!nodes || n_nodes < 1)) return -2;
+    ctx_t c = {tris, n_tris, NULL, 0, nodes, n_nodes, NULL, mode};
+    for (int64_t i = 0; i < n; i++) {
+        uint64_t tests = 0, visits = 0;
+        hit_t h = closest_from(&c, mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]),
+                               bound[i], &tests, &visits);
+        out_dst[i] = h.dst;
+        out_tri[i] = h.tri;
+        if (out_tests) out_tests[i] = tests;
+        if (out_visits) out_visits[i] = visits;
+    }
+    return 0;
 }
 
 /* Single-call helpers for known-answer tests. */

@@ -64,6 +64,14 @@ int oracle_render_pixels(const oracle_triangle* tris, int32_t n_tris, const orac
                          uint32_t frame_count, const int32_t* px, int64_t n_px, int32_t mode, int32_t threads,
                          float* out_accum, uint32_t* out_acc8, uint64_t* out_segments, uint64_t* out_tests);
 
+/* The closest hit of n rays (o, d: n * 3 floats), each scan started at
+ * r.dst = bound[i]: mode 0 = the array scan, 1 = the BVH walk over `nodes`.
+ * A miss keeps dst = bound[i] and tri = -1.  out_tests / out_visits
+ * (nullable): per-ray leaf triangle tests and interior nodes popped. */
+int oracle_closest_hits(const oracle_triangle* tris, int32_t n_tris, const oracle_node* nodes, int32_t n_nodes,
+                        const float* o, const float* d, const float* bound, int64_t n, int32_t mode, float* out_dst,
+                        int32_t* out_tri, uint64_t* out_tests, uint64_t* out_visits);
+
 /* Textures for TEXTURE materials (global to the library): n stb-layout
  * images, whn = (width, height, channels) triples.  n = 0 clears. */
 int oracle_set_textures(const int32_t* whn, const uint8_t* const* pixels, int32_t n);

@@ -22,6 +22,7 @@ PATHS = ("auto", "scalar")
 F32 = np.float32
 
 _scenes = {}
+_nodes = {}  # (scene, triangles) -> the node array of its BVH scene
 
 
 def _scene(rt2mod, kind, n, bvh=False):
@@ -35,6 +36,7 @@ def _scene(rt2mod, kind, n, bvh=False):
             scene.set_traversal("bvh")
             up = sd.triangles()
             up.setflags(write=False)
+            _nodes[(kind, n)] = sd.nodes()
         else:
             scene, up = rt2mod.Scene(triangles=tris, materials=mats), tris
         _scenes[key] = (scene, up)
@@ -199,8 +201,14 @@ def test_scene_outside_the_filters_range(rt2mod, oraclemod, path):
 
 @pytest.mark.parametrize("n", (1217, 8193))
 def test_bvh_traversal(rt2mod, oraclemod, n):
-    """Tie-free soups: the BVH walk's result is the array scan's over the
-    triangles as uploaded (build_bvh reorders them), unbounded and bounded."""
+    """The BVH walk against the array scan over the triangles as uploaded
+    (build_bvh reorders them), unbounded and bounded.  The scan is a valid
+    reference for the walk here, and only here: the soups have no exact
+    distance ties (the walk visits the leaves in another order than the scan,
+    so a tie could go to another triangle), and build_bvh's boxes are tight
+    around their triangles (a box never hides a hit the scan finds).  On trees
+    without these properties (tests/test_gpu_bvh_edges.py) only the oracle's
+    own walk is the reference; it is checked here as well."""
     nr = 193 if n == 1217 else 97
     o, d = T.scene_rays("soup", n, nr)
     scene, up = _scene(rt2mod, "soup", n, bvh=True)
@@ -208,6 +216,13 @@ def test_bvh_traversal(rt2mod, oraclemod, n):
     assert ties.max() == 1
     _same(scene.trace_rays(o, d), dst, tri, f"bvh {n}")
     assert scene.last_kernel() == rt2mod.QUERY_BVH
+    nodes = _nodes[("soup", n)]
+    wd, wt, wtests, wvisits = oraclemod.closest_hits(up, o, d, None, "bvh", nodes)
+    _same(scene.trace_rays(o, d), wd, wt, f"bvh {n} against the oracle's walk")
+    scene.stats(reset=True)
+    scene.trace_rays(o, d)
+    st = scene.stats(reset=True)
+    assert st.tests == int(wtests.sum()) and st.node_visits == int(wvisits.sum())
     # bounds by turns one ulp above the hit (the same hit), halfway to it (a miss) and none
     hit, i = tri >= 0, np.arange(nr)
     tmax = np.select([hit & (i % 3 == 0), hit & (i % 3 == 1)],
