@@ -54,6 +54,14 @@
 // follow it; in a kernel whose first window is the whole scene (353, 354) it
 // never exists and the T1 records are not brought into LDS.
 // MfmaSpec::y_first keeps the Y product there (the A/B arms).
+//
+// MfmaSpec::exact_lanes (353, 354): the episode tests per ray, not per wave.
+// A hot triangle is hot for about 3 of the wave's 64 rays, so the window's hot
+// triangles are compacted into synthetic groups of 32 whose products, with the
+// operands exchanged, give every ray its own pass mask, and each lane tests
+// only its own pairs (exact_window_lanes below; DESIGN.md "Exact tests per
+// ray").  The filter's guarantee is per (ray, triangle) pair, so this skips
+// only tests the reference would reject.
 #pragma once
 
 namespace {
@@ -87,6 +95,186 @@ __device__ __forceinline__ bool exact_group(unsigned long long M, int G, int n_t
     return __ballot(bestK != bk0) != 0;
 }
 
+// diag: one episode's MfmaDiag::xl counts from each lane's pairs and its `k`
+// (the wave's largest k is what a per-lane test loop would run)
+__device__ __forceinline__ void xl_counts(MfmaDiag& dg, int pairs, int k, int rounds) {
+    for (int off = 32; off > 0; off >>= 1) {
+        pairs += __shfl_xor(pairs, off);
+        k = max(k, __shfl_xor(k, off));
+    }
+    const unsigned long long kw = (unsigned long long)__builtin_amdgcn_readfirstlane(k);
+    dg.xl[0] += (unsigned long long)__builtin_amdgcn_readfirstlane(pairs);
+    dg.xl[1] += kw;
+    dg.xl[2] += (unsigned long long)rounds;
+    dg.xl[3] = kw > dg.xl[3] ? kw : dg.xl[3];
+}
+
+// MfmaSpec::exact_lanes.  A ray's 32-bit mask of a round: bit b is the b-th
+// hot triangle of the round in ascending index, and it comes out of the
+// transposed product's row xl_row_of_bit(b): lane l of the product's result
+// holds ray l & 31 in all 16 registers, register r being row 8 (r >> 2) +
+// 4 (l >> 5) + (r & 3); the two lanes of a ray pack their registers into bits
+// 0..15 (l < 32) and 16..31.
+__host__ __device__ constexpr int xl_row_of_bit(int b) { return 8 * ((b & 15) >> 2) + 4 * (b >> 4) + (b & 3); }
+__host__ __device__ constexpr int xl_bit_of_row(int r) { return 16 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3); }
+
+// The exact episode of one window with the tests per ray (MfmaSpec::
+// exact_lanes) instead of per wave.  exact_window runs every hot triangle's
+// test on all 64 lanes, though only a few rays asked for it.  Here:
+//   - compaction: the window's hot triangles (maskv, the scene's last group
+//     cut to n_tris) in ascending index, 32 per round, are listed in `lst`
+//     (lane s = the index of the round's s-th) by a scalar walk of the masks:
+//     per hot triangle a compare and a v_cndmask beside its SALU, no LDS and
+//     no per-lane loop;
+//   - gather: a kt record is per triangle column (lane t + 32 h of a group's
+//     operand holds triangle t's k-slots 8 h .. 8 h + 7: prep_mfma_kt), so a
+//     16-byte read at per-lane addresses makes a valid operand out of any 32
+//     triangles.  Lane l reads the triangle of bit xl_bit_of_row(l & 31);
+//     slots past the round's count read triangle 0's record and their bits
+//     are cleared;
+//   - transposed products: mfma(records, a0[R]) instead of mfma(a0[R],
+//     records).  The A and B layouts of the 32x32x16 product are the same, so
+//     the operands are the ones kt_group takes; the result's lanes are rays;
+//   - pack: the same 16 ANDs as kt_group (with Y when the window has it),
+//     then 16 v_alignbit (mask << 1 | sign) per block and one
+//     v_permlane32_swap, after which lane l holds its own ray's 32 bits;
+//   - every lane walks its own bits, lowest first: the triangle by vector
+//     loads, then the unchanged mt_quantities / mt_pass3 / mt_exact.
+// Rounds ascend and a lane's bits ascend, so every ray sees its surviving
+// pairs in index order against its current bound: the sequential strict `dst <
+// best` scan.  The filter's guarantee is per (ray, triangle) pair (DESIGN.md
+// "Exact tests per ray"), so a ray may skip what other rays of its wave test.
+// upper = false: lanes 32..63 hold no ray of their own and get a zero mask.
+// LDS: the records of every group of the window are resident (recs = the
+// LDS copy); else recs = the scene's kt records in global memory.
+template <MfmaSpec S, bool YP, bool LDS, class Rebuild>
+__device__ __forceinline__ void exact_window_lanes(int maskv, int Gw, bool more, int n_tris, const float4* tri4,
+                                                   const h8* a0, const h8* y1, const h8* recs, bool upper, const f3& o,
+                                                   const f3& d, float& best, int& bi, float& bestK, MfmaDiag& dg,
+                                                   Rebuild rebuild) {
+    const int lane = (int)lane_id();
+    [[maybe_unused]] unsigned long long tc = 0;
+    if constexpr (S.diag) {
+        dg.claims += 1;
+        tc = __builtin_amdgcn_s_memtime();
+    }
+    // padding slots of the scene's last group never enter the list
+    if (n_tris & 31) maskv = lane == (n_tris >> 5) - Gw ? maskv & (int)((1u << (n_tris & 31)) - 1u) : maskv;
+    unsigned long long hotg = __ballot(maskv != 0);
+    if constexpr (S.diag) dg.hot += (unsigned long long)__popcll(hotg);
+    const float bk0 = bestK;
+    const int src = 4 * xl_bit_of_row(lane & 31);  // ds_bpermute address of the list entry this lane gathers
+    const f16v zero = {};
+    uint32_t m = 0;  // the current group's triangles still to be listed
+    int gj = 0;      // ... its lane of maskv
+    [[maybe_unused]] int pairs = 0, iters = 0, rounds = 0;
+#pragma nounroll
+    for (;;) {
+        int lst = 0, c = 0;
+#pragma nounroll
+        while (c < 32) {
+            if (!m) {
+                if (!hotg) break;
+                gj = __builtin_ctzll(hotg);
+                hotg &= hotg - 1;
+                m = (uint32_t)__builtin_amdgcn_readlane(maskv, gj);
+            }
+            const int idx = 32 * (Gw + gj) + __builtin_ctz(m);
+            m &= m - 1;
+            lst = lane == c ? idx : lst;
+            c++;
+        }
+        if (!c) break;
+        if constexpr (S.diag) {
+            dg.exact += (unsigned long long)c;
+            rounds += 1;
+        }
+        // this lane's row of the synthetic group
+        const int T = __builtin_amdgcn_ds_bpermute(src, lst);
+        const h8* rp = recs + ((T >> 5) * (kKtOps * 64) + (T & 31) + (lane & 32));
+        // One block's products and its 16-bit mask: kt_group's three products
+        // and 16 ANDs at its peak of 48 product registers (the episode has
+        // those and no more), then Y on its own where the window has it.  The
+        // empty asm statements pin a stage's results in registers before the
+        // next one starts: without them the compiler runs both blocks'
+        // products side by side (96 registers) and spills the path state.
+        auto block = [&](int R) {
+            int t3[16];
+            {
+                const f16v U = __builtin_amdgcn_mfma_f32_32x32x16_f16(rp[0], a0[R], zero, 0, 0, 0);
+                const f16v V = __builtin_amdgcn_mfma_f32_32x32x16_f16(rp[64], a0[R], zero, 0, 0, 0);
+                const f16v X = __builtin_amdgcn_mfma_f32_32x32x16_f16(rp[128], a0[R], zero, 0, 0, 0);
+#pragma unroll
+                for (int i = 0; i < 16; i++)  // U & V & X, as kt_group
+                    t3[i] = __builtin_amdgcn_bitop3_b32(__float_as_int(U[i]), __float_as_int(V[i]),
+                                                        __float_as_int(X[i]), 0x80);
+            }
+            if constexpr (YP) {
+                asm volatile("" : "+v"(t3[0]), "+v"(t3[1]), "+v"(t3[2]), "+v"(t3[3]), "+v"(t3[4]), "+v"(t3[5]),
+                             "+v"(t3[6]), "+v"(t3[7]), "+v"(t3[8]), "+v"(t3[9]), "+v"(t3[10]), "+v"(t3[11]),
+                             "+v"(t3[12]), "+v"(t3[13]), "+v"(t3[14]), "+v"(t3[15]));
+                const f16v Yt = __builtin_amdgcn_mfma_f32_32x32x16_f16(rp[192], y1[R], zero, 0, 0, 0);
+#pragma unroll
+                for (int i = 0; i < 16; i++) t3[i] &= __float_as_int(Yt[i]);
+            }
+            int mk = 0;
+#pragma unroll
+            for (int i = 15; i >= 0; i--)  // mk << 1 | sign: register i ends in bit i
+                mk = (int)__builtin_amdgcn_alignbit((uint32_t)mk, (uint32_t)t3[i], 31);
+            asm volatile("" : "+v"(mk));
+            return mk;
+        };
+        const int mk0 = block(0);
+        int mk1 = 0;
+        if (upper) mk1 = block(1);
+        // lanes 0..31: block 0's two halves of ray l; lanes 32..63: block 1's
+        const auto sw = __builtin_amdgcn_permlane32_swap((uint32_t)mk0, (uint32_t)mk1, false, false);
+        uint32_t pm = (sw[0] | sw[1] << 16) & (c == 32 ? ~0u : (1u << c) - 1u);
+        if constexpr (S.diag) pairs += __popc(pm);
+        // The lane's pairs, lowest bit first.  The mask is known up front, so
+        // the next pair's triangle is requested before the current test runs
+        // (a lane without a further bit reads entry 31 of the list, a valid
+        // index or 0, and never uses it).
+        auto entry = [&](uint32_t m) { return __builtin_amdgcn_ds_bpermute(4 * __builtin_ctz(m | 0x80000000u), lst); };
+        struct Tri {
+            int idx;
+            float4 t0, t1, t2;
+        };
+        auto fetch = [&](Tri& t) {
+            t.idx = entry(pm);
+            t.t0 = tri4[3 * t.idx], t.t1 = tri4[3 * t.idx + 1], t.t2 = tri4[3 * t.idx + 2];
+        };
+        // one pair: request the next triangle into `nxt`, test `cur`
+        auto step = [&](const Tri& cur, Tri& nxt) {
+            if constexpr (S.diag) iters += 1;
+            const bool has = pm != 0;
+            pm &= pm - 1;
+            fetch(nxt);
+            if (has) {
+                const MtQ qq = mt_quantities(o, d, cur.t0, cur.t1, cur.t2);
+                if (mt_pass3(qq, bestK)) mt_exact(qq, cur.idx, best, bi, bestK);
+            }
+        };
+        Tri ta, tb2;
+        fetch(ta);
+        // two steps per trip, the two triangles' registers changing roles (no copies, and no wait for the
+        // requested triangle before the trip's end)
+#pragma nounroll
+        while (__ballot(pm != 0)) {
+            step(ta, tb2);
+            if (!__ballot(pm != 0)) break;
+            step(tb2, ta);
+        }
+        if (c < 32) break;
+    }
+    if constexpr (S.diag) xl_counts(dg, pairs, iters, rounds);
+    if (more && __ballot(bestK != bk0)) {
+        if constexpr (S.diag) tc = __builtin_amdgcn_s_memtime();
+        rebuild();
+        if constexpr (S.diag) dg.t_pub += __builtin_amdgcn_s_memtime() - tc;
+    }
+}
+
 // The exact episode of one window of cnt groups from group Gw on: group Gw +
 // j's hot mask is lane j of maskv (exact_win = 1: m1).  The groups in
 // ascending order, each mask's triangles in ascending index, the same tests as
@@ -112,6 +300,10 @@ __device__ __forceinline__ void exact_window(uint32_t m1, int maskv, int Gw, int
         dg.t_issue += t - tc;
     }
     const float bk0 = bestK;
+    // diag: this lane's pairs that pass the filter's own three conditions
+    // (mt_pass3's U, -V and X terms on the exact quantities: what the products
+    // decide in a window without Y), and the episode's tested triangles
+    [[maybe_unused]] int pairs = 0, tested = 0;
     for (int j = 0; j < cnt; j++) {
         uint32_t m32 = mask_of(j);
         if constexpr (S.diag) dg.hot += m32 != 0;
@@ -123,9 +315,15 @@ __device__ __forceinline__ void exact_window(uint32_t m1, int maskv, int Gw, int
             if constexpr (S.diag) dg.exact += 1;
             cfloat* tp = tri + 12 * idx;
             const MtQ qq = mt_quantities(o, d, ldc4(tp), ldc4(tp + 4), ldc4(tp + 8));
+            if constexpr (S.diag) {
+                const float X = __builtin_fmaf(-qq.det, 1.0009765625f, qq.V - qq.U);
+                pairs += fmaxf(fmaxf(qq.U, -qq.V), X) <= qq.det * 0x1p-60f;
+                tested += 1;
+            }
             if (mt_pass3(qq, bestK)) mt_exact(qq, idx, best, bi, bestK);
         }
     }
+    if constexpr (S.diag) xl_counts(dg, pairs, pairs, (tested + 31) >> 5);
     if (more && __ballot(bestK != bk0)) {
         if constexpr (S.diag) tc = __builtin_amdgcn_s_memtime();
         rebuild();
@@ -236,8 +434,22 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
             if (any) {
                 const bool more = YP && (Gw + cnt < ng || (W == 1 && !S.y_skip_last));
                 if (resident) phase_prio<S>(1);
-                exact_window<S>(any, maskv, Gw, cnt, more, n_tris, tri, o, d, best, bi, bestK, dg,
-                                [&] { kt_y(d, o, bestK, sc, tw16, y1); });
+                if constexpr (S.exact_lanes) {
+                    static_assert(W > 1, "exact_lanes reads the window's masks from maskv");
+                    const float4* tri4 = reinterpret_cast<const float4*>(p.tri);
+                    auto rebuild = [&] { kt_y(d, o, bestK, sc, tw16, y1); };
+                    // a first window is resident; the L2 loop's windows gather from the scene's records
+                    if (!YP || resident)
+                        exact_window_lanes<S, YP, true>(maskv, Gw, more, n_tris, tri4, a0, y1, rec, upper, o, d, best,
+                                                        bi, bestK, dg, rebuild);
+                    else if constexpr (YP)
+                        exact_window_lanes<S, YP, false>(maskv, Gw, more, n_tris, tri4, a0, y1,
+                                                         reinterpret_cast<const h8*>(p.mfma_kt_frag), upper, o, d, best,
+                                                         bi, bestK, dg, rebuild);
+                } else {
+                    exact_window<S>(any, maskv, Gw, cnt, more, n_tris, tri, o, d, best, bi, bestK, dg,
+                                    [&] { kt_y(d, o, bestK, sc, tw16, y1); });
+                }
                 if (resident) phase_prio<S>(0);
             }
             // a window of kResGroups is the whole sweep of a kernel without the L2 loop
@@ -471,6 +683,10 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
             atomicAdd(p.seg_counter + 17, dg.t_issue);  // ... of the exact phase: waiting for an episode's first triangle
             atomicAdd(p.seg_counter + 18, dg.t_pub);    // ... of the exact phase: the Y rebuilds
             atomicAdd(p.seg_counter + 19, dg.claims);   // exact episodes
+            atomicAdd(p.seg_counter + 7, dg.xl[0]);     // per episode (MfmaDiag::xl): (ray, triangle) pairs
+            atomicAdd(p.seg_counter + 8, dg.xl[1]);     // ... the largest count of one ray
+            atomicAdd(p.seg_counter + 9, dg.xl[2]);     // ... rounds of 32 hot triangles
+            atomicMax(p.seg_counter + 10, dg.xl[3]);    // the largest count of one ray in any episode
         }
 }
 

@@ -64,17 +64,27 @@ struct MfmaSpec {
     bool y_first = false;  // render_mfma_k5r, window path: a sweep's first window runs the Y product too (no ray has a
                            // bound there, so Y is the det > 0 test that U, -V, X imply); false: kt_group<false>, and
                            // the Y fragment is first built after that window
+    bool exact_lanes = false;  // render_mfma_k5r, window path: the episode tests per ray, not per wave: the window's
+                               // hot triangles are compacted into synthetic groups whose transposed products give
+                               // every ray its own pass mask (rt2_k5_resident.h exact_window_lanes)
 };
 
 // per-wave diagnostic counts (wave-uniform; MfmaSpec::diag)
 struct MfmaDiag {
     unsigned long long groups = 0, hot = 0, exact = 0;
-    // The two `unused` members are not read.  They keep the struct's 15 words
-    // and its members' places: kernels built without diag never touch a
-    // MfmaDiag, yet its size changes the registers the compiler assigns in
-    // them (the same instructions on other registers), and with this layout
-    // their code is the code DESIGN.md's measurements are of.
-    unsigned long long unused0[4] = {};
+    // `unused1` is not read, and `xl` only by sweep_kt_res's diagnostic
+    // builds.  They keep the struct's 15 words and its members' places:
+    // kernels built without diag never touch a MfmaDiag, yet its size changes
+    // the registers the compiler assigns in them (the same instructions on
+    // other registers), and with this layout their code is the code
+    // DESIGN.md's measurements are of.
+    // sweep_kt_res, per exact episode: [0] (ray, triangle) pairs that pass the
+    // filter's U, -V, X conditions (exact_window: evaluated on the exact
+    // quantities; exact_window_lanes: the bits of the rays' masks), summed
+    // over the lanes; [1] the largest such count of one lane (exact_window_
+    // lanes: the per-lane loop's iterations), summed over the episodes; [2]
+    // rounds of 32 hot triangles; [3] the largest [1] of one episode
+    unsigned long long xl[4] = {};
     // shader clocks (s_memtime) per wave: waiting for a tile (render_mfma_k5r:
     // the sweep's ray setup), the products (with the records' LDS reads), the
     // exact phase (with the Y rebuilds), the whole sweep

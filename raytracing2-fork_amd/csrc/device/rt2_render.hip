@@ -590,6 +590,11 @@ constexpr MfmaSpec kt_yw(MfmaSpec x) {
     return x;
 }
 #endif
+// ... with the exact tests per ray (MfmaSpec::exact_lanes; rt2_k5_resident.h exact_window_lanes)
+constexpr MfmaSpec kt_xl(MfmaSpec x) {
+    x.exact_lanes = true;
+    return x;
+}
 constexpr int kResWin = 38;  // the window of 353-356 (and the diagnostic 350): the whole resident sweep, then one episode
 constexpr int kResL2Groups = 256;  // render_mfma_k5r with res_l2: kResGroups groups resident, the rest from L2
 // records streamed through LDS tiles (rt2_k5_tiles.h): 19-group tiles, each ray's own W, issue priority by
@@ -632,9 +637,10 @@ constexpr Variant kVariants[] = {
     // records in LDS for the whole launch, 38 groups, the rest read from L2) with the threshold in the K-slots
     // (DESIGN.md "The threshold in the K-slots"), each ray's own W, issue priority by phase; fair-share issue
     // priority instead for rank slabs; the exact phase once per window of kResWin groups, the first window of a sweep
-    // without the Y product (DESIGN.md "No Y product without a bound")
-    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 4), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
-    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, true, true), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
+    // without the Y product (DESIGN.md "No Y product without a bound"); 353 / 354 run the exact tests per ray
+    // (DESIGN.md "Exact tests per ray")
+    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
+    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(false, true, true), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
     RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, true, 4), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
     RT2_VARIANT(356, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, true, true), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw", kResL2Groups),
     // the default above 8,192 triangles: the LDS-tiled kernel (rt2_k5_tiles.h; 19-group tiles, fragments in
@@ -671,6 +677,13 @@ constexpr Variant kVariants[] = {
     RT2_VARIANT(351, K_MFMA, render_mfma_k5r<kt_yw(kt_win(kt_res(false, false, true, 4), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/yw", kResGroups),
     RT2_VARIANT(352, K_MFMA, render_mfma_k5r<kt_yw(kt_win(kt_res(true, false, true, 4), kResWin))>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4/yw", kResL2Groups),
     RT2_VARIANT(357, K_MFMA, render_mfma_k5r<kt_yw(kt_win(kt_res(false, false, true, 0, true), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/yw", kResGroups),
+    // the exact tests per ray from a compacted hot-triangle pass (MfmaSpec::exact_lanes; 353 / 354 take it): the
+    // wave-wide episode on 353's and 354's spec (xwave: the form before), the per-ray one on 355's, 350's and 356's (xl)
+    RT2_VARIANT(400, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, false, true, 4), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/xwave", kResGroups),
+    RT2_VARIANT(401, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(true, false, true, 4), kResWin))>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4/xl", kResL2Groups),
+    RT2_VARIANT(402, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(false, false, true, 0, true), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/xl", kResGroups),
+    RT2_VARIANT(403, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, true, true), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/xwave", kResGroups),
+    RT2_VARIANT(404, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(true, true, true), kResWin))>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw/xl", kResL2Groups),
     // the tile stream at 3 waves per SIMD (380 takes 4 with the lean lane state): with its diagnostic clocks; without
     // flow_prio; with the lean lane state
     RT2_VARIANT(370, K_MFMA, render_mfma_k5t<kt_tiles_flow()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp"),
@@ -1198,6 +1211,7 @@ constexpr MfmaSpec kQueryResL2 = kt_win(kt_res(true, false, true, 4), kResWin);
 // render's 350), 2 = the Y product in the first window too, which a caller's tmax can prune with (the render's 351)
 constexpr MfmaSpec kQueryResDiag = kt_win(kt_res(false, false, true, 0, true), kResWin);
 constexpr MfmaSpec kQueryResYw = kt_yw(kQueryRes);
+constexpr MfmaSpec kQueryResXl = kt_xl(kQueryRes);  // 3 = the exact tests per ray (the render's 400)
 #endif
 constexpr int kQueryBlock = 256;                  // trace_rays_scalar
 constexpr long long kQuerySlice = 1ll << 30;      // rays per trace_rays_scalar launch (its grid: 2^22 blocks)
@@ -1206,10 +1220,10 @@ enum : int { Q_RES = -2, Q_RES_L2 = -3, Q_SCALAR = -4, Q_BVH = -5 };
 }  // namespace
 
 #ifdef RT2_EXPERIMENTS
-// Not in rt2.h (experiment build): 0 = the product kernel, 1 / 2 = kQueryResDiag / kQueryResYw for scenes of at most
-// kResGroups groups.
+// Not in rt2.h (experiment build): 0 = the product kernel, 1 / 2 / 3 = kQueryResDiag / kQueryResYw / kQueryResXl for
+// scenes of at most kResGroups groups.
 extern "C" int rt2_scene_set_query_arm(rt2_scene* s, int arm) {
-    if (!s || arm < 0 || arm > 2) return -1;
+    if (!s || arm < 0 || arm > 3) return -1;
     s->query_arm = arm;
     return 0;
 }
@@ -1258,6 +1272,8 @@ extern "C" int rt2_trace_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, rt
             hipLaunchKernelGGL(trace_rays_k5r<kQueryResDiag>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
         else if (resident && s->query_arm == 2)
             hipLaunchKernelGGL(trace_rays_k5r<kQueryResYw>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
+        else if (resident && s->query_arm == 3)
+            hipLaunchKernelGGL(trace_rays_k5r<kQueryResXl>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
         else
 #endif
         if (resident)

@@ -3,7 +3,10 @@ resident kernel 391 with the default window and per group, and the tile stream
 370, plus counters; experiment build, RT2_LIB=exp): per (wave, 32-triangle
 group) sweep, how often a pair passes the filter (the wave enters the exact
 phase) and how many (wave, triangle) exact tests follow; for the resident
-kernel also its phase clocks."""
+kernel also its phase clocks and, per exact episode, the (ray, triangle) pairs,
+the busiest ray's pairs and the rounds of 32 hot triangles (350: counted on
+the exact quantities; 402, the per-ray episode MfmaSpec::exact_lanes: what
+it ran)."""
 import argparse
 import ctypes as C
 import json
@@ -67,6 +70,17 @@ for v in [int(x) for x in a.variants.split(",")]:
                                           tests=round((ex - load - reb) / max(episodes, 1), 1),
                                           y_rebuild=round(reb / max(episodes, 1), 1),
                                           whole=round(ex / max(episodes, 1), 1)))
+        # MfmaDiag::xl: per episode, the (ray, triangle) pairs that pass the filter's U, -V, X conditions, the
+        # largest count of one ray (what a per-lane test loop runs; exact_lanes arms: its iterations) and the
+        # rounds of 32 hot triangles
+        pairs, ksum, rounds, kmax = c[8], c[9], c[10], c[11]
+        if rounds:
+            res[name_of(v)].update(
+                lanes=dict(hot_triangles_per_episode=round(exact / max(episodes, 1), 2),
+                           pairs_per_episode=round(pairs / max(episodes, 1), 2),
+                           pairs_per_hot_triangle=round(pairs / max(exact, 1), 2),
+                           k_per_episode=round(ksum / max(episodes, 1), 2), k_max=kmax,
+                           rounds_per_episode=round(rounds / max(episodes, 1), 3)))
 vs = list(imgs)
 res["bit_identical"] = all(bool((imgs[v] == imgs[vs[0]]).all()) for v in vs[1:])
 print(json.dumps(res, indent=1))
