@@ -24,9 +24,11 @@ zero, so the R rays of a pixel start alike, and
     of one emission, and that sample directions over the hemisphere all hit.
 Anything else raises NotDeterministic.  One-channel textures (their texels
 cannot keep max(rayColor) at 1 next to the r,r,r swizzle unless they are 255
-throughout), partial specular probability, survival below 1 and the cosine
-distribution of the diffuse scatter cannot be made deterministic; they stay
-with the bit-exact oracle tests and are not approximated here.
+throughout), partial specular probability, survival below 1 and the diffuse
+scatter cannot be made deterministic and are not approximated here:
+tests/random_path_model.py follows them with the shader's own draws
+(tests/test_random_paths.py, tests/test_gpu_random_paths.py).  One-channel
+textures stay with the bit-exact oracle tests.
 
 Comparison rule (assert_image): f32 and f64 may decide differently on a pixel
 that straddles an edge, a texel boundary or a checker line, and a value near a
