@@ -251,6 +251,45 @@ int rt2_trace_rays(rt2_scene* scene, const rt2_ray* d_rays, int64_t n, rt2_hit* 
 int rt2_trace_rays_host(rt2_scene* scene, const rt2_ray* rays, int64_t n, rt2_hit* hits, int flags);
 
 /* ------------------------------------------------------------------------
+ * (1a') Occlusion queries: is anything in front of a caller's ray?
+ *
+ * occluded[i] is 1 when rt2_trace_rays on the same scene, traversal and ray
+ * would return tri >= 0, and 0 otherwise; no other byte value is written and
+ * no byte outside [0, n) is written:
+ *   - bound_i is as in (1a): tmax when 0 < tmax < 1e38f, otherwise 1e38f, so
+ *     a zero-filled field means unbounded.  The comparison is strict;
+ *   - RT2_TRAVERSAL_BRUTE: some triangle of the array as uploaded has
+ *     rayTriangleIntersect (compute.glsl:302-340) hit with dst < bound_i;
+ *   - RT2_TRAVERSAL_BVH: calculateRayCollisionBVH (compute.glsl:410-460)
+ *     started at best = bound_i accepts some hit (needs `nodes` at
+ *     rt2_scene_create).  The definition is the walk's, not the array scan's:
+ *     on trees whose boxes do not enclose their triangles the two can differ;
+ *   - the query stops at a ray's first accepted hit.  That is exact: until the
+ *     first accept the closest-hit scan's best is still bound_i, and after it
+ *     tri never returns to -1;
+ *   - d need not be normalised; o and d may be any floats.  A ray with a
+ *     non-finite component is unoccluded and does not disturb the other rays
+ *     of the call.
+ * rt2_occluded reads d_rays and writes d_occluded in DEVICE memory (n records
+ * and n bytes; d_rays aligned to 16 bytes, d_occluded with no alignment
+ * requirement) and is asynchronous on `stream`; its ordering against the
+ * scene's other launches is rt2_trace_rays'.  n == 0 returns 0 and launches
+ * nothing.  Bad arguments (a null scene, n < 0, a null pointer with n > 0, a
+ * misaligned d_rays, unknown flag bits, BVH traversal on a scene without
+ * nodes) return < 0 before any device call.
+ * rt2_scene_stats counts a query as segments += n.  Brute force: tests is the
+ * nominal segments * N, as for every brute-force launch, not the tests an
+ * early exit left undone.  BVH: tests and node_visits count what the walk did
+ * up to its exit.
+ * flags: RT2_TRACE_AUTO and RT2_TRACE_SCALAR, with the meaning they have for
+ * rt2_trace_rays.  Every choice gives the same bytes.
+ * rt2_occluded_host is the blocking form over host arrays: its device staging
+ * buffers are kept by the scene between calls and freed by rt2_scene_destroy.
+ * ---------------------------------------------------------------------- */
+int rt2_occluded(rt2_scene* scene, const rt2_ray* d_rays, int64_t n, uint8_t* d_occluded, int flags, void* stream);
+int rt2_occluded_host(rt2_scene* scene, const rt2_ray* rays, int64_t n, uint8_t* occluded, int flags);
+
+/* ------------------------------------------------------------------------
  * (1b) Multi-GPU: row-tile shards + one RCCL gather
  *
  * The reference renders on one GPU and reads the framebuffer back with

@@ -44,6 +44,7 @@ using namespace rt2d;
 #include "rt2_bvh.h"
 #include "rt2_misc_kernels.h"
 #include "rt2_query.h"
+#include "rt2_occluded.h"
 
 /* =========================================================================
  * C-ABI, device half
@@ -125,6 +126,11 @@ struct rt2_scene {
     rt2_hit* d_query_hits = nullptr;
     size_t query_cap = 0;           // rays the two buffers hold
     int query_arm = 0;                // experiment build: A/B arm of the resident query kernel
+    // rt2_occluded_host: staging buffers, kept like the above
+    rt2_ray* d_occluded_rays = nullptr;
+    uint8_t* d_occluded_out = nullptr;
+    size_t occluded_cap = 0;          // rays the two buffers hold
+    int occluded_arm = 0;             // experiment build: A/B arm of occluded_k5r
     unsigned long long* d_region_ctr = nullptr;  // 8 item-region counters, 128 B apart
     unsigned long long* wave_log = nullptr;  // diagnostic wave timeline (rt2_scene_set_wave_log)
     uint32_t wave_log_n = 0;
@@ -505,6 +511,8 @@ extern "C" void rt2_scene_destroy(rt2_scene* s) {
     (void)hipFree(s->d_host_rgb8);
     (void)hipFree(s->d_query_rays);
     (void)hipFree(s->d_query_hits);
+    (void)hipFree(s->d_occluded_rays);
+    (void)hipFree(s->d_occluded_out);
     (void)hipFree(s->d_region_ctr);
     if (s->host_stream) (void)hipStreamDestroy(s->host_stream);
     delete s;
@@ -1334,6 +1342,168 @@ extern "C" int rt2_trace_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n,
     HIPCHECK(hipMemcpyAsync(s->d_query_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
     if (rt2_trace_rays(s, s->d_query_rays, n, s->d_query_hits, flags, st) != 0) return -1;
     HIPCHECK(hipMemcpyAsync(hits, s->d_query_hits, (size_t)n * sizeof(rt2_hit), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+/* -------------------------------------------------------------------------
+ * Occlusion queries (rt2_occluded.h)
+ * ----------------------------------------------------------------------- */
+namespace {
+// occluded_k5r: trace_rays_k5r's frame, windows of `win` groups, no Y product (y = false: a frame whose resident
+// form leaves the T1 records out of LDS) or the Y product
+// from the second window on; wave = the episode per wave (any_window_wave) instead of per ray
+constexpr OccSpec occ_spec(bool l2, int win, bool y, bool wave) {
+    return OccSpec{kt_win(kt_res(l2, false, true, 4), y ? win : kResWin), win, y, wave};
+}
+// The shipped window and Y choice (DESIGN.md §Occlusion queries, profiles/occluded_ab.json); the L2 form takes the
+// resident form's.
+constexpr int kOccWin = 3;
+constexpr bool kOccY = false;
+constexpr bool kOccWave = true;
+constexpr OccSpec kOccRes = occ_spec(false, kOccWin, kOccY, kOccWave);
+constexpr OccSpec kOccResL2 = occ_spec(true, kOccWin, kOccY, kOccWave);
+// after kQuery's codes: what rt2_scene_diag reports as the variant last launched
+enum : int { O_RES = -6, O_RES_L2 = -7, O_SCALAR = -8, O_BVH = -9 };
+
+template <OccSpec O>
+void launch_occluded_k5r(unsigned blocks, hipStream_t st, const RenderParams& p, const OccParams& q) {
+    hipLaunchKernelGGL(occluded_k5r<O>, dim3(blocks), dim3(O.m.block), 0, st, p, q);
+}
+}  // namespace
+
+#ifdef RT2_EXPERIMENTS
+// Not in rt2.h (experiment build): the A/B arms of occluded_k5r, for the resident and the L2 form alike.  0 = the
+// product kernel; 1 = a window of kResWin without Y (no exit inside the resident stretch: the control); 2, 3 =
+// windows of 12 and 6 groups without Y; 4, 5 = those windows with the Y product from the second window on; 6 = a
+// window of 3 groups without Y; 7 .. 10 = windows of kResWin, 12, 6 and 3 groups without Y and the episode per wave
+// instead of per ray.
+extern "C" int rt2_scene_set_occluded_arm(rt2_scene* s, int arm) {
+    if (!s || arm < 0 || arm > 10) return -1;
+    s->occluded_arm = arm;
+    return 0;
+}
+#endif
+
+extern "C" int rt2_occluded(rt2_scene* s, const rt2_ray* d_rays, int64_t n, uint8_t* d_occluded, int flags,
+                            void* stream) {
+    if (!s || n < 0 || (n > 0 && (!d_rays || !d_occluded)) || (flags & ~RT2_TRACE_SCALAR) ||
+        (reinterpret_cast<uintptr_t>(d_rays) & 15)) {
+        rt2h::set_error("rt2_occluded: bad argument (a scene, n >= 0, rays aligned to 16 B, flags 0 or "
+                        "RT2_TRACE_SCALAR)");
+        return -1;
+    }
+    if (n == 0) return 0;
+    const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
+    if (bvh && s->n_nodes == 0) {
+        rt2h::set_error("rt2_occluded: bad argument (BVH traversal needs the node array)");
+        return -1;
+    }
+    HIPCHECK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.tri = s->d_tri;
+    p.n_tris = s->n_tris;
+    p.mfma_A = s->mfma_A;
+    p.mfma_kt_frag = s->d_mfma_kt;
+    p.nodes = s->d_nodes;
+    p.stack_slots = s->bvh_depth + 2;
+    p.item_counter = s->d_counters;
+    p.seg_counter = s->d_counters + 1;
+    OccParams q{d_rays, d_occluded, (long long)n};
+    // the kernel choice of rt2_trace_rays
+    const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
+    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
+    if (matrix) {
+        const unsigned blocks = (unsigned)std::min<long long>(s->num_cus, (n + 1023) / 1024);
+        const bool resident = (s->n_tris + 31) / 32 <= kResGroups;
+        int arm = 0;
+#ifdef RT2_EXPERIMENTS
+        arm = s->occluded_arm;
+#endif
+        auto go = [&](auto res, auto l2) {
+            if (resident)
+                launch_occluded_k5r<decltype(res)::value>(blocks, st, p, q);
+            else
+                launch_occluded_k5r<decltype(l2)::value>(blocks, st, p, q);
+        };
+        switch (arm) {
+#ifdef RT2_EXPERIMENTS
+#define RT2_OCC_ARM(A, W, Y, V)                                                                       \
+    case A:                                                                                           \
+        go(std::integral_constant<OccSpec, occ_spec(false, W, Y, V)>{},                               \
+           std::integral_constant<OccSpec, occ_spec(true, W, Y, V)>{});                               \
+        break;
+            RT2_OCC_ARM(1, kResWin, false, false)
+            RT2_OCC_ARM(2, 12, false, false)
+            RT2_OCC_ARM(3, 6, false, false)
+            RT2_OCC_ARM(4, 12, true, false)
+            RT2_OCC_ARM(5, 6, true, false)
+            RT2_OCC_ARM(6, 3, false, false)
+            RT2_OCC_ARM(7, kResWin, false, true)
+            RT2_OCC_ARM(8, 12, false, true)
+            RT2_OCC_ARM(9, 6, false, true)
+            RT2_OCC_ARM(10, 3, false, true)
+#undef RT2_OCC_ARM
+#endif
+        default:
+            go(std::integral_constant<OccSpec, kOccRes>{}, std::integral_constant<OccSpec, kOccResL2>{});
+        }
+        HIPCHECK(hipGetLastError());
+        s->last_kind = K_MFMA;
+        s->last_variant = resident ? O_RES : O_RES_L2;
+    } else {
+        for (long long i0 = 0; i0 < (long long)n; i0 += kQuerySlice) {
+            q.rays = d_rays + i0;
+            q.out = d_occluded + i0;
+            q.n = std::min<long long>(kQuerySlice, (long long)n - i0);
+            const unsigned blocks = (unsigned)((q.n + kQueryBlock - 1) / kQueryBlock);
+            if (bvh)
+                hipLaunchKernelGGL((occluded_scalar<kQueryBlock, true>), dim3(blocks), dim3(kQueryBlock),
+                                   (size_t)p.stack_slots * kQueryBlock * sizeof(int), st, p, q);
+            else
+                hipLaunchKernelGGL((occluded_scalar<kQueryBlock, false>), dim3(blocks), dim3(kQueryBlock), 0, st, p,
+                                   q);
+            HIPCHECK(hipGetLastError());
+        }
+        s->last_kind = bvh ? K_BVH : K_SMEM;
+        s->last_variant = bvh ? O_BVH : O_SCALAR;
+    }
+    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(s->last_launch, st));
+    s->last_launch_valid = true;
+    s->tests_per_seg = (unsigned long long)s->n_tris;
+    return 0;
+}
+
+extern "C" int rt2_occluded_host(rt2_scene* s, const rt2_ray* rays, int64_t n, uint8_t* occluded, int flags) {
+    if (!s || n < 0 || (n > 0 && (!rays || !occluded)) || (flags & ~RT2_TRACE_SCALAR)) {
+        rt2h::set_error("rt2_occluded_host: bad argument (a scene, n >= 0, flags 0 or RT2_TRACE_SCALAR)");
+        return -1;
+    }
+    if (n == 0) return 0;
+    if (s->traversal == RT2_TRAVERSAL_BVH && s->n_nodes == 0) {
+        rt2h::set_error("rt2_occluded_host: bad argument (BVH traversal needs the node array)");
+        return -1;
+    }
+    HIPCHECK(hipSetDevice(s->device));
+    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    hipStream_t st = s->host_stream;
+    if ((size_t)n > s->occluded_cap) {
+        HIPCHECK(hipStreamSynchronize(st));
+        (void)hipFree(s->d_occluded_rays);
+        (void)hipFree(s->d_occluded_out);
+        s->d_occluded_rays = nullptr;
+        s->d_occluded_out = nullptr;
+        s->occluded_cap = 0;
+        HIPCHECK(hipMalloc(&s->d_occluded_rays, (size_t)n * sizeof(rt2_ray)));
+        HIPCHECK(hipMalloc(&s->d_occluded_out, (size_t)n));
+        s->occluded_cap = (size_t)n;
+    }
+    HIPCHECK(hipMemcpyAsync(s->d_occluded_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
+    if (rt2_occluded(s, s->d_occluded_rays, n, s->d_occluded_out, flags, st) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(occluded, s->d_occluded_out, (size_t)n, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     return 0;
 }

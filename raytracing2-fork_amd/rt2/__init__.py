@@ -159,6 +159,7 @@ HIT_DTYPE = np.dtype([("dst", "<f4"), ("tri", "<i4")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 8
 TRACE_AUTO, TRACE_SCALAR = 0, 1  # RT2_TRACE_AUTO, RT2_TRACE_SCALAR
 QUERY_RES, QUERY_RES_L2, QUERY_SCALAR, QUERY_BVH = -2, -3, -4, -5  # Scene.last_kernel after a query
+OCCLUDED_RES, OCCLUDED_RES_L2, OCCLUDED_SCALAR, OCCLUDED_BVH = -6, -7, -8, -9  # ... after an occlusion query
 
 # Every symbol include/rt2.h declares (tests check the library exports them all).
 EXPORTED = [
@@ -175,7 +176,7 @@ EXPORTED = [
     "rt2_uniforms_offline", "rt2_write_png", "rt2_image_load", "rt2_image_free", "rt2_sd_texture",
     "rt2_scene_set_textures", "rt2_comm_unique_id", "rt2_comm_init", "rt2_comm_wrap", "rt2_comm_destroy",
     "rt2_comm_size", "rt2_comm_check", "rt2_gather_slabs", "rt2_unshard_slabs", "rt2_render_host_gather",
-    "rt2_comm_wait", "rt2_trace_rays", "rt2_trace_rays_host",
+    "rt2_comm_wait", "rt2_trace_rays", "rt2_trace_rays_host", "rt2_occluded", "rt2_occluded_host",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -217,6 +218,8 @@ def lib() -> C.CDLL:
         "rt2_render_host": (C.c_int, [P, C.POINTER(Uniforms), U32, U32, Shard, P, P]),
         "rt2_trace_rays": (C.c_int, [P, P, I64, P, C.c_int, P]),
         "rt2_trace_rays_host": (C.c_int, [P, P, I64, P, C.c_int]),
+        "rt2_occluded": (C.c_int, [P, P, I64, P, C.c_int, P]),
+        "rt2_occluded_host": (C.c_int, [P, P, I64, P, C.c_int]),
         "rt2_resolve_rgba32f": (C.c_int, [P, I64, U32, P, P]),
         "rt2_resolve_rgb8_reference": (C.c_int, [P, I64, U32, P]),
         "rt2_scene_stats": (C.c_int, [P, C.POINTER(Stats), C.c_int]),
@@ -619,10 +622,37 @@ class Scene:
                                     C.c_void_p(hits_ptr) if hits_ptr else None, int(flags),
                                     C.c_void_p(stream) if stream else None), "rt2_trace_rays")
 
+    def occluded(self, origins, directions, tmax=None, flags: int = 0) -> np.ndarray:
+        """Whether anything lies in front of each of n rays before its bound
+        (rt2_occluded_host, blocking): the arguments of trace_rays; returns
+        bool[n], equal to trace_rays(...)[1] >= 0 without the closest hit being
+        found (a ray stops at its first accepted hit)."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise RT2Error(f"occluded: {len(o)} origins for {len(d)} directions")
+        rays = np.zeros(len(o), dtype=RAY_DTYPE)
+        rays["o"], rays["d"] = o, d
+        if tmax is not None:
+            rays["tmax"] = np.asarray(tmax, dtype=np.float32)
+        out = np.full(len(o), 0xAA, dtype=np.uint8)
+        _check(lib().rt2_occluded_host(self._p, rays.ctypes.data, len(rays), out.ctypes.data, int(flags)),
+               "rt2_occluded_host")
+        if (out > 1).any():
+            raise RT2Error("rt2_occluded_host wrote a byte other than 0 or 1")
+        return out.astype(bool)
+
+    def occluded_device(self, rays_ptr: int, n: int, out_ptr: int, flags: int = 0, stream: int = 0) -> None:
+        """Asynchronous occlusion query over a device array of n rt2_ray records into n bytes (rt2_occluded)."""
+        _check(lib().rt2_occluded(self._p, C.c_void_p(rays_ptr) if rays_ptr else None, int(n),
+                                  C.c_void_p(out_ptr) if out_ptr else None, int(flags),
+                                  C.c_void_p(stream) if stream else None), "rt2_occluded")
+
     def last_kernel(self) -> int:
         """What the scene launched last (rt2_scene_diag): a render's variant id (-1: the traceBasic preview), or
         after a query QUERY_RES (trace_rays_k5r, every group resident), QUERY_RES_L2 (its L2 continuation),
-        QUERY_SCALAR or QUERY_BVH (trace_rays_scalar)."""
+        QUERY_SCALAR or QUERY_BVH (trace_rays_scalar); after an occlusion query OCCLUDED_RES, OCCLUDED_RES_L2
+        (occluded_k5r), OCCLUDED_SCALAR or OCCLUDED_BVH (occluded_scalar)."""
         c, v = (C.c_ulonglong * 8)(), C.c_int(-1)
         if lib().rt2_scene_diag(self._p, c, C.byref(v)) != 0:
             raise RT2Error("rt2_scene_diag failed")

@@ -16,6 +16,9 @@
 #   PMC="B C E"      PMC passes (scripts/profile_pmc.sh) of the bench's render kernel per config
 #   TRACE_AB=<rounds>  ray-query A/B, matrix against scalar kernel (scripts/trace_rays_ab.py): rewrites
 #                    profiles/trace_rays_ab.json and prints its summary; TRACE_AB_OUT=<file> writes there instead
+#   OCC_AB=<rounds>  occlusion-query A/B against rt2_trace_rays, every arm of the experiment build
+#                    (scripts/occluded_ab.py; needs rt2/librt2_exp.so): rewrites profiles/occluded_ab.json;
+#                    OCC_AB_OUT=<file> writes there instead
 #   TAG=<name>       suffix of the output files
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
@@ -56,6 +59,11 @@ if [ -n "${TRACE_AB}" ]; then
   timeout -k 10 900 python -u scripts/trace_rays_ab.py --rounds "${TRACE_AB}" ${TRACE_AB_OUT:+--out "$TRACE_AB_OUT"} \
     || { echo "ray-query A/B failed"; exit 1; }
   echo "ray-query A/B ok"
+fi
+if [ -n "${OCC_AB}" ]; then
+  timeout -k 10 1100 python -u scripts/occluded_ab.py --rounds "${OCC_AB}" ${OCC_AB_OUT:+--out "$OCC_AB_OUT"} \
+    || { echo "occlusion-query A/B failed"; exit 1; }
+  echo "occlusion-query A/B ok"
 fi
 if [ -n "${BENCH}" ]; then
   bargs="${BENCH}"; [ "${BENCH}" = default ] && bargs="--full"
