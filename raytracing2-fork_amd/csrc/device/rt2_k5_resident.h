@@ -62,7 +62,20 @@
 // only its own pairs (exact_window_lanes below; DESIGN.md "Exact tests per
 // ray").  The filter's guarantee is per (ray, triangle) pair, so this skips
 // only tests the reference would reject.
+//
+// MfmaSpec::pair_loop (353, 354): the products' loop takes two groups per
+// trip and writes each hot mask into its lane of the mask register with one
+// v_writelane (sweep_kt_res).  MfmaSpec::cam_park (353, 354): the kernels that
+// never load the T1 pieces keep every lane's camera end point in the wave's
+// own T1 piece, written once per pixel-frame and read once per ray
+// (render_mfma_k5r; rt2_path.h advance<.., PARK>).  Neither changes a value
+// that reaches the image.
 #pragma once
+
+// v_writelane_b32 (value and lane wave-uniform).  clang has a builtin for
+// readlane but none for writelane; a declaration under the intrinsic's own name
+// reaches it, and the compiler places the lane select (m0 on gfx9) itself.
+extern "C" __device__ int rt2_writelane(int value, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
 
 namespace {
 
@@ -419,15 +432,44 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
             const int cnt = W == 1 ? 1 : min(W, G1 - Gw);
             int maskv = 0;
             uint32_t any = 0;
-            for (int j = 0; j < cnt; j++) {
-                const h8 b0 = tb[0], b1 = tb[64], b2 = tb[128];
-                h8 b3 = {};
-                if constexpr (YP) b3 = tb[192];
-                tb += kKtOps * 64;
-                const unsigned long long M = kt_group<YP>(a0, y1, b0, b1, b2, b3, upper);
-                const uint32_t m32 = (uint32_t)(M | M >> 32);
-                if constexpr (W > 1) maskv = lane == j ? (int)m32 : maskv;
-                any |= m32;
+            if constexpr (S.pair_loop && W > 1) {
+                // MfmaSpec::pair_loop.  Two groups per trip: the second one's
+                // records sit a constant 4 KiB behind the first's, so its
+                // ds_read_b128 take immediate offsets and the pointer steps
+                // once per pair.  The ballot's mask and the group's number are
+                // wave-uniform, so one v_writelane puts the mask into lane j
+                // (the loop below pays a v_mov, a compare and a select).
+                // kt_group keeps its own basic blocks and scheduling groups.
+                auto group = [&](const h8* t, int j) {
+                    const h8 b0 = t[0], b1 = t[64], b2 = t[128];
+                    h8 b3 = {};
+                    if constexpr (YP) b3 = t[192];
+                    const unsigned long long M = kt_group<YP>(a0, y1, b0, b1, b2, b3, upper);
+                    const uint32_t m32 = (uint32_t)(M | M >> 32);
+                    maskv = rt2_writelane((int)m32, j, maskv);
+                    any |= m32;
+                };
+                int j = 0;
+                for (; j + 1 < cnt; j += 2) {
+                    group(tb, j);
+                    group(tb + kKtOps * 64, j + 1);
+                    tb += 2 * kKtOps * 64;
+                }
+                if (j < cnt) {
+                    group(tb, j);
+                    tb += kKtOps * 64;
+                }
+            } else {
+                for (int j = 0; j < cnt; j++) {
+                    const h8 b0 = tb[0], b1 = tb[64], b2 = tb[128];
+                    h8 b3 = {};
+                    if constexpr (YP) b3 = tb[192];
+                    tb += kKtOps * 64;
+                    const unsigned long long M = kt_group<YP>(a0, y1, b0, b1, b2, b3, upper);
+                    const uint32_t m32 = (uint32_t)(M | M >> 32);
+                    if constexpr (W > 1) maskv = lane == j ? (int)m32 : maskv;
+                    any |= m32;
+                }
             }
             if constexpr (S.diag) dg.groups += (unsigned long long)cnt;
             if (resident) stamp(dg.t_filt);
@@ -544,6 +586,7 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
     Lane L;
     lane_init(L);
     MfmaDiag dg;
+    [[maybe_unused]] PathDiagSlot<S.diag> pds;
     const int wave = (int)(threadIdx.x >> 6);
     // MfmaSpec::lean: the wave counts its lanes' segments (no per-lane counter)
     [[maybe_unused]] unsigned long long segs_w = 0;
@@ -558,7 +601,24 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
     }
     for (;;) {
         const RenderParams& p = kargs<RenderParams>();
-        advance<1, !S.lean>(L, p);
+        if constexpr (S.cam_park) {
+            // MfmaSpec::cam_park.  This kernel never loads the T1 pieces
+            // (no_t1 above; piece 4 G + 3 of group G) and K5Resident holds
+            // kResGroups >= NW groups whatever the scene's size, so wave w
+            // keeps its lanes' end points in the T1 piece of group w: no LDS
+            // added, no other wave reads or writes it, no barrier.
+            constexpr bool no_t1 = !S.y_first && S.exact_win >= kResGroups && !S.res_l2;
+            static_assert(no_t1 && S.lean && NW <= kResGroups, "cam_park parks in T1 pieces that nothing else uses");
+            float4* park = reinterpret_cast<float4*>(&rs.rec[(4 * wave + 3) * 64 + (int)lane_id()]);
+            if constexpr (S.diag)
+                advance<1, false, true, true>(L, p, park, pds.get());
+            else
+                advance<1, false, true>(L, p, park);
+        } else if constexpr (S.diag) {
+            advance<1, !S.lean, false, true>(L, p, nullptr, pds.get());
+        } else {
+            advance<1, !S.lean>(L, p);
+        }
         unsigned long long act = __ballot(L.st == ST_TRACE);
         if constexpr (S.lean) segs_w += (unsigned long long)__popcll(act);
         if constexpr (S.diag) {
@@ -580,7 +640,10 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
             if (L.st == ST_TRACE) {
                 L.bounce += 1;
                 if constexpr (!S.lean) L.segs += 1;
-                shade(L, p, mybest, mybi);
+                if constexpr (S.diag)
+                    shade<1, true>(L, p, mybest, mybi, pds.get());
+                else
+                    shade(L, p, mybest, mybi);
             }
             continue;
         }
@@ -614,6 +677,11 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
                 const bool live = (act >> l) & 1ull;
                 const int to = 4 * (int)(live ? lanes_below(act) : nl + lanes_below(~act));
                 lane_permute<!S.lean, !S.lean>(L, to);
+                if constexpr (S.cam_park) {  // the parked end point travels with its path state
+                    float4* park = reinterpret_cast<float4*>(&rs.rec[(4 * wave + 3) * 64 + (int)lane_id()]);
+                    const float4 e = *park;
+                    *park = make_float4(perm_f(to, e.x), perm_f(to, e.y), perm_f(to, e.z), 0.0f);
+                }
                 act = __ballot(L.st == ST_TRACE);
             }
             upper = false;
@@ -641,7 +709,10 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
         if (mine) {
             L.bounce += 1;
             if constexpr (!S.lean) L.segs += 1;
-            shade(L, p, best, bi);
+            if constexpr (S.diag)
+                shade<1, true>(L, p, best, bi, pds.get());
+            else
+                shade(L, p, best, bi);
         }
     }
     const RenderParams& p = kargs<RenderParams>();
@@ -670,6 +741,17 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
                 e[9] = c1;
             }
         }
+    if constexpr (S.diag) {  // PathDiag: rnd_dir calls and loop trips of the wave (the lanes' counts summed)
+        unsigned long long calls = pds.d.rd_calls, trips = pds.d.rd_trips;
+        for (int off = 32; off > 0; off >>= 1) {
+            calls += __shfl_xor(calls, off);
+            trips += __shfl_xor(trips, off);
+        }
+        if (lane_id() == 0) {
+            atomicAdd(p.seg_counter + 20, calls);
+            atomicAdd(p.seg_counter + 21, trips);
+        }
+    }
     if constexpr (S.diag)
         if (lane_id() == 0) {
             atomicAdd(p.seg_counter + 1, dg.groups);  // (wave, triangle group) sweeps
@@ -687,6 +769,8 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
             atomicAdd(p.seg_counter + 8, dg.xl[1]);     // ... the largest count of one ray
             atomicAdd(p.seg_counter + 9, dg.xl[2]);     // ... rounds of 32 hot triangles
             atomicMax(p.seg_counter + 10, dg.xl[3]);    // the largest count of one ray in any episode
+            atomicAdd(p.seg_counter + 22, pds.d.new_ray);  // PathDiag: advance's new-ray block, executions
+            atomicAdd(p.seg_counter + 23, pds.d.new_px);   // ... its new-frame block
         }
 }
 

@@ -96,6 +96,26 @@ __device__ __forceinline__ f3 rnd_dir(uint32_t& state) {
     return divs(p, __builtin_sqrtf(s));  // normalize(p)
 }
 
+// rnd_dir for diagnostic builds: trips += 1 per trip of the loop in the first
+// of the lanes that run it, so the sum over a wave's lanes counts the wave's
+// trips.
+__device__ __forceinline__ f3 rnd_dir_counted(uint32_t& state, uint32_t& trips) {
+    f3 p = mk(0.0f, 0.0f, 0.0f);
+    float s = 0.0f;
+    bool ok = false;
+    for (int i = 0; i < 100 && !ok; i++) {
+        trips += (uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x) == threadIdx.x;
+        float x = rnd(state) * 2.0f - 1.0f;
+        float y = rnd(state) * 2.0f - 1.0f;
+        float z = rnd(state) * 2.0f - 1.0f;
+        p = mk(x, y, z);
+        s = dot(p, p);
+        ok = s < 1.0f;
+    }
+    if (!ok) return mk(0.0f, 0.0f, 0.0f);
+    return divs(p, __builtin_sqrtf(s));
+}
+
 // refract_, compute.glsl:201-214
 __device__ __forceinline__ f3 refract_(f3 I, f3 N, float eta, bool& isRefracted) {
     float k = 1.0f - eta * eta * (1.0f - dot(N, I) * dot(N, I));

@@ -67,6 +67,12 @@ struct MfmaSpec {
     bool exact_lanes = false;  // render_mfma_k5r, window path: the episode tests per ray, not per wave: the window's
                                // hot triangles are compacted into synthetic groups whose transposed products give
                                // every ray its own pass mask (rt2_k5_resident.h exact_window_lanes)
+    bool pair_loop = false;  // render_mfma_k5r, window path: two groups per trip of the products' loop (the second
+                             // group's records at immediate offsets, one pointer step per pair) and each group's hot
+                             // mask put into its lane of maskv by one v_writelane
+    bool cam_park = false;   // render_mfma_k5r without the T1 pieces (no_t1): a pixel's camera end point is computed
+                             // once per pixel-frame and parked in the lane's 16 bytes of the wave's own unused T1
+                             // piece; a new ray reads it back (rt2_path.h advance<.., PARK>)
 };
 
 // per-wave diagnostic counts (wave-uniform; MfmaSpec::diag)

@@ -6,8 +6,9 @@
 namespace {
 
 // Per-lane path state, kept small (VGPRs decide the waves per SIMD): the
-// camera end point is recomputed per ray and the frame sums go straight to the
-// accumulators in HBM (one read-modify-write per pixel-frame).
+// camera end point is recomputed per ray (or parked in LDS per pixel-frame:
+// advance<.., PARK>) and the frame sums go straight to the accumulators in HBM
+// (one read-modify-write per pixel-frame).
 struct Lane {
     int st;
     uint32_t item;
@@ -19,6 +20,29 @@ struct Lane {
     bool inside;
     f3 o, d, rayColor, incoming, colorCum;
     uint32_t segs;
+};
+
+// Counts of the work outside the sweep (diagnostic builds of render_mfma_k5r;
+// a null pointer everywhere else).  rd_calls, rd_trips: per lane, += 1 in the
+// first of the lanes that run a rnd_dir call / a trip of its loop, so their
+// sums over the wave are the wave's executions; new_ray, new_px: wave-uniform,
+// advance's ST_NEW_RAY and ST_NEW_FRAME blocks entered by at least one lane.
+struct PathDiag {
+    uint32_t rd_calls = 0, rd_trips = 0;
+    unsigned long long new_ray = 0, new_px = 0;
+};
+
+// ... a kernel's own: empty unless the build counts (a PathDiag among a
+// kernel's locals changes the registers the compiler assigns even where
+// nothing reads it, as MfmaDiag's size does)
+template <bool ON>
+struct PathDiagSlot {
+    __device__ __forceinline__ PathDiag* get() { return nullptr; }
+};
+template <>
+struct PathDiagSlot<true> {
+    PathDiag d;
+    __device__ __forceinline__ PathDiag* get() { return &d; }
 };
 
 // S > 1: split mode (render_split) — the S waves of a workgroup hold the same
@@ -40,13 +64,28 @@ __device__ __forceinline__ void item_xy(uint32_t item, const RenderParams& p, in
     y = shard_row(lr, p.tile_rows, p.rank, p.nranks);
 }
 
+// endPoint of pixel (x, y), compute.glsl:665-670
+__device__ __forceinline__ f3 camera_end_point(int x, int y, const RenderParams& p) {
+    const float px = (float)(x * 2 - p.W) / (float)p.W;
+    const float py = (float)(y * 2 - p.H) / (float)p.H;
+    return add(add(add(ld3(p.cam), ld3(p.vpFront)), muls(ld3(p.vpRight), px)), muls(ld3(p.vpUp), py));
+}
+
 // Phase A: bring every lane to ST_TRACE or ST_DONE (wave-collective; with
 // S > 1 workgroup-collective, every wave of the group on the same path).
 // XY = false: L.x, L.y are not kept across calls (recomputed from L.item
 // where a new frame or ray needs them: two VGPRs less live across the sweep
-// of the register-bound resident kernel)
-template <int S = 1, bool XY = true>
-__device__ __forceinline__ void advance(Lane& L, const RenderParams& p) {
+// of the register-bound resident kernel).
+// PARK (with XY = false): the camera end point depends on the pixel only, so
+// it is computed where a pixel-frame starts (ST_NEW_FRAME: the item's
+// division, px, py and their two IEEE divisions) and kept in `park`, 16 bytes
+// of LDS that belong to this lane alone; each of the pixel's rays reads it
+// back.  The same operations on the same inputs, so the same bits.  A caller
+// that moves path states between lanes moves the parked value with them.
+template <int S = 1, bool XY = true, bool PARK = false, bool PD = false>
+__device__ __forceinline__ void advance(Lane& L, const RenderParams& p, float4* park = nullptr,
+                                        PathDiag* pd = nullptr) {
+    static_assert(!PARK || !XY, "the parked end point replaces the per-ray recomputation of advance<S, false>");
     for (;;) {
         const bool need = L.st == ST_NEED_ITEM;
         unsigned long long m = __ballot(need);
@@ -107,8 +146,18 @@ __device__ __forceinline__ void advance(Lane& L, const RenderParams& p) {
                 }
             }
         }
-        if constexpr (!XY)
+        if constexpr (PD) {
+            pd->new_px += __any(L.st == ST_NEW_FRAME) ? 1u : 0u;
+            pd->new_ray += __any(L.st == ST_NEW_FRAME || L.st == ST_NEW_RAY) ? 1u : 0u;
+        }
+        if constexpr (!XY && !PARK)
             if (L.st == ST_NEW_FRAME || L.st == ST_NEW_RAY) item_xy(L.item, p, L.x, L.y);
+        if constexpr (PARK)
+            if (L.st == ST_NEW_FRAME) {
+                item_xy(L.item, p, L.x, L.y);
+                const f3 e = camera_end_point(L.x, L.y, p);
+                *park = make_float4(e.x, e.y, e.z, 0.0f);
+            }
         if (L.st == ST_NEW_FRAME) {
             // compute.glsl:662-670
             const uint32_t f = p.frame_begin + L.frame;
@@ -119,10 +168,15 @@ __device__ __forceinline__ void advance(Lane& L, const RenderParams& p) {
         }
         if (L.st == ST_NEW_RAY) {
             // compute.glsl:665-670 (endPoint, recomputed per ray) and :685-690
-            const float px = (float)(L.x * 2 - p.W) / (float)p.W;
-            const float py = (float)(L.y * 2 - p.H) / (float)p.H;
-            const f3 endPoint =
-                add(add(add(ld3(p.cam), ld3(p.vpFront)), muls(ld3(p.vpRight), px)), muls(ld3(p.vpUp), py));
+            f3 endPoint;
+            if constexpr (PARK) {
+                const float4 e = *park;
+                endPoint = mk(e.x, e.y, e.z);
+            } else {
+                const float px = (float)(L.x * 2 - p.W) / (float)p.W;
+                const float py = (float)(L.y * 2 - p.H) / (float)p.H;
+                endPoint = add(add(add(ld3(p.cam), ld3(p.vpFront)), muls(ld3(p.vpRight), px)), muls(ld3(p.vpUp), py));
+            }
             float ang = rnd(L.seed);
             float cs = rt2pm_cosf(ang), sn = rt2pm_sinf(ang);
             L.o = add(add(ld3(p.cam), muls(ld3(p.defR), cs)), muls(ld3(p.defU), sn));
@@ -229,8 +283,18 @@ __device__ __forceinline__ f3 texture_color(const RenderParams& p, int tex_index
 }
 
 // Phase C: scatter at the closest hit (compute.glsl:485-559).
-template <int S = 1>
-__device__ __forceinline__ void shade(Lane& L, const RenderParams& p, float best, int bi) {
+// PD (diagnostic builds): the rnd_dir calls and their trips are counted in *pd.
+template <bool PD>
+__device__ __forceinline__ f3 shade_rnd_dir(uint32_t& seed, PathDiag* pd) {
+    if constexpr (PD) {
+        pd->rd_calls += (uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x) == threadIdx.x;
+        return rnd_dir_counted(seed, pd->rd_trips);
+    } else {
+        return rnd_dir(seed);
+    }
+}
+template <int S = 1, bool PD = false>
+__device__ __forceinline__ void shade(Lane& L, const RenderParams& p, float best, int bi, PathDiag* pd = nullptr) {
     if (bi >= 0) {
         const int mi = p.tri_mtl[bi];
         // the texture lookup first, while little else is live (it needs the
@@ -250,11 +314,11 @@ __device__ __forceinline__ void shade(Lane& L, const RenderParams& p, float best
         switch (m.materialType) {
         case RT2_DIFFUSE:
         case RT2_TEXTURE:
-            L.d = normalize(add(normal, rnd_dir(L.seed)));
+            L.d = normalize(add(normal, shade_rnd_dir<PD>(L.seed, pd)));
             atten = m.materialType == RT2_DIFFUSE ? xyz4(m.color) : tex;
             break;
         case RT2_SPECULAR: {
-            f3 diffuseDir = normalize(add(normal, rnd_dir(L.seed)));
+            f3 diffuseDir = normalize(add(normal, shade_rnd_dir<PD>(L.seed, pd)));
             f3 specDir = reflect(L.d, normal);
             bool isSpec = m.specularProbability > rnd(L.seed);
             L.d = mixs(diffuseDir, specDir, isSpec ? m.smoothness : 0.0f);
@@ -268,7 +332,7 @@ __device__ __forceinline__ void shade(Lane& L, const RenderParams& p, float best
             return;
         }
         case RT2_CHECKER: {
-            L.d = normalize(add(normal, rnd_dir(L.seed)));
+            L.d = normalize(add(normal, shade_rnd_dir<PD>(L.seed, pd)));
             float s = m.checkerScale;
             bool black = false;
             if (s > 0.0f) {

@@ -603,6 +603,16 @@ constexpr MfmaSpec kt_xl(MfmaSpec x) {
     x.exact_lanes = true;
     return x;
 }
+// ... with two groups per trip of the products' loop and the hot masks by v_writelane (MfmaSpec::pair_loop), and with
+// the camera end point parked per pixel-frame (MfmaSpec::cam_park; kernels without the T1 pieces only)
+constexpr MfmaSpec kt_pair(MfmaSpec x) {
+    x.pair_loop = true;
+    return x;
+}
+constexpr MfmaSpec kt_park(MfmaSpec x) {
+    x.cam_park = true;
+    return x;
+}
 constexpr int kResWin = 38;  // the window of 353-356 (and the diagnostic 350): the whole resident sweep, then one episode
 constexpr int kResL2Groups = 256;  // render_mfma_k5r with res_l2: kResGroups groups resident, the rest from L2
 // records streamed through LDS tiles (rt2_k5_tiles.h): 19-group tiles, each ray's own W, issue priority by
@@ -646,9 +656,11 @@ constexpr Variant kVariants[] = {
     // (DESIGN.md "The threshold in the K-slots"), each ray's own W, issue priority by phase; fair-share issue
     // priority instead for rank slabs; the exact phase once per window of kResWin groups, the first window of a sweep
     // without the Y product (DESIGN.md "No Y product without a bound"); 353 / 354 run the exact tests per ray
-    // (DESIGN.md "Exact tests per ray")
-    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
-    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(false, true, true), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
+    // (DESIGN.md "Exact tests per ray"), two groups per trip of the products' loop with the hot masks by v_writelane
+    // (DESIGN.md "Two groups per loop trip") and keep each pixel's camera end point in LDS instead of recomputing it
+    // per ray (DESIGN.md "The camera end point once per pixel")
+    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
+    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
     RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, true, 4), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
     RT2_VARIANT(356, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, true, true), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw", kResL2Groups),
     // the default above 8,192 triangles: the LDS-tiled kernel (rt2_k5_tiles.h; 19-group tiles, fragments in
@@ -692,6 +704,13 @@ constexpr Variant kVariants[] = {
     RT2_VARIANT(402, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(false, false, true, 0, true), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/xl", kResGroups),
     RT2_VARIANT(403, K_MFMA, render_mfma_k5r<kt_win(kt_res(false, true, true), kResWin)>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/xwave", kResGroups),
     RT2_VARIANT(404, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(true, true, true), kResWin))>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw/xl", kResL2Groups),
+    // two groups per loop trip with the masks by v_writelane, and the parked camera end point (MfmaSpec::pair_loop,
+    // cam_park; 353 / 354 take both): 353's spec with neither (the form before), with pair_loop only, with cam_park
+    // only; 354's with neither
+    RT2_VARIANT(405, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/nopair/nopark", kResGroups),
+    RT2_VARIANT(406, K_MFMA, render_mfma_k5r<kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/nopark", kResGroups),
+    RT2_VARIANT(407, K_MFMA, render_mfma_k5r<kt_park(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/nopair", kResGroups),
+    RT2_VARIANT(408, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(false, true, true), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/nopair/nopark", kResGroups),
     // the tile stream at 3 waves per SIMD (380 takes 4 with the lean lane state): with its diagnostic clocks; without
     // flow_prio; with the lean lane state
     RT2_VARIANT(370, K_MFMA, render_mfma_k5t<kt_tiles_flow()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp"),

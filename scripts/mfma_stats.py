@@ -70,6 +70,18 @@ for v in [int(x) for x in a.variants.split(",")]:
                                           tests=round((ex - load - reb) / max(episodes, 1), 1),
                                           y_rebuild=round(reb / max(episodes, 1), 1),
                                           whole=round(ex / max(episodes, 1), 1)))
+        # PathDiag (rt2_path.h): the work outside the sweep per wave-segment (a wave's sweep): rnd_dir calls (one per
+        # material kind the wave's hits have) and the trips of their rejection loops, advance's new-ray and
+        # new-frame blocks
+        rd_calls, rd_trips, new_ray, new_px = c[21], c[22], c[23], c[24]
+        if rd_calls:
+            res[name_of(v)].update(
+                outside_sweep=dict(wave_segments=int(sweeps), rnd_dir_calls=rd_calls, rnd_dir_trips=rd_trips,
+                                   rnd_dir_calls_per_wave_segment=round(rd_calls / max(sweeps, 1), 4),
+                                   rnd_dir_trips_per_call=round(rd_trips / rd_calls, 3),
+                                   rnd_dir_trips_per_wave_segment=round(rd_trips / max(sweeps, 1), 3),
+                                   new_ray_blocks_per_wave_segment=round(new_ray / max(sweeps, 1), 4),
+                                   new_frame_blocks_per_wave_segment=round(new_px / max(sweeps, 1), 4)))
         # MfmaDiag::xl: per episode, the (ray, triangle) pairs that pass the filter's U, -V, X conditions, the
         # largest count of one ray (what a per-lane test loop runs; exact_lanes arms: its iterations) and the
         # rounds of 32 hot triangles
