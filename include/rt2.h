@@ -290,6 +290,79 @@ int rt2_occluded(rt2_scene* scene, const rt2_ray* d_rays, int64_t n, uint8_t* d_
 int rt2_occluded_host(rt2_scene* scene, const rt2_ray* rays, int64_t n, uint8_t* occluded, int flags);
 
 /* ------------------------------------------------------------------------
+ * (1a'') Surface queries: what is at the closest hit of a caller's rays
+ *
+ * out[i] is the reference's HitInfo (compute.glsl:97-106) at ray i's closest
+ * hit, plus the surface's base colour:
+ *   - dst and tri are exactly what rt2_trace_rays returns for the same scene,
+ *     traversal, flags and ray: the tmax rule of (1a), the strict comparison,
+ *     the ties, the BVH visiting order and the treatment of non-finite rays.
+ * On a hit:
+ *   - mtl = tris[tri].materialIndex and mtl_type = mats[mtl].materialType;
+ *   - normal = normalize(cross(b - a, c - a)), the value the renderer scatters
+ *     about (compute.glsl:331): one bit pattern per triangle, whatever the
+ *     ray.  rayTriangleIntersect culls back faces (det < 0 is no hit), so
+ *     dot(normal, d) < 0 at every hit: the normal always faces the ray;
+ *   - u, v are the barycentrics of rayTriangleIntersect (compute.glsl:
+ *     322-337) with the test's own arithmetic, as getTriangleTextureColor
+ *     recomputes them: inv = 1 / det, u = -U * inv, v = V * inv, the weights
+ *     of b and c; the weight of a is 1 - u - v (HitInfo.baryCoord is
+ *     (1 - u - v, u, v)).  u >= 0, v >= 0 and 1 - u - v >= 0 hold exactly in
+ *     binary32 (the test accepted them).  The reference's own texture lookup
+ *     pairs them otherwise, uv = aTex * u + bTex * v + cTex * (1 - u - v)
+ *     (compute.glsl:342-347); albedo follows the reference there;
+ *   - albedo is what traceBasic (compute.glsl:565-645) returns for this ray
+ *     with maxBounceCount = 1 and basicShadingShadow = 0: material.color for
+ *     DIFFUSE, SPECULAR and GLASS; the sampled texel for TEXTURE
+ *     (getTriangleTextureColor at the ray's own o, d); 0 or 1 for CHECKER,
+ *     evaluated at hitPoint - normal * 1e-4; normalizeColor(emissionColor)
+ *     for LIGHT (divided by its largest component only when that exceeds 1);
+ *     black for GLASS_HIGHLIGHT; magenta (1, 0, 1) for any other type.
+ *     A ray query has no uniforms: the reference's numTextures is taken as
+ *     the number of images given to rt2_scene_set_textures, at most 5 (the
+ *     shader's units), so a textureIndex at or above it reads black.
+ * On a miss tri = mtl = mtl_type = -1, dst = bound_i, and normal, u, albedo
+ * and v are +0.0: there is no sky colour without uniforms.
+ * rt2_surface_rays reads d_rays and writes d_out in DEVICE memory (n records
+ * each, both aligned to 16 bytes, as any hipMalloc'ed array is), nothing
+ * outside records [0, n), and is asynchronous on `stream`; its ordering
+ * against the scene's other launches is rt2_trace_rays'.  n == 0 returns 0
+ * and launches nothing.  Bad arguments (a null scene, n < 0, a null or
+ * misaligned pointer with n > 0, unknown flag bits, BVH traversal on a scene
+ * without nodes) return < 0 before any device call.  rt2_scene_stats counts
+ * it as it counts rt2_trace_rays.
+ * flags: RT2_TRACE_AUTO and RT2_TRACE_SCALAR, with the meaning they have for
+ * rt2_trace_rays.  Every choice gives the same bytes.
+ * rt2_surface_rays_host is the blocking form over host arrays (no alignment
+ * requirement): its device staging buffers are kept by the scene between
+ * calls and freed by rt2_scene_destroy.
+ *
+ * rt2_camera_rays writes the deterministic primary ray of every pixel of the
+ * shard's slab, in slab-row order (rt2_shard_rows(height, shard) * width
+ * records, DEVICE memory aligned to 16 bytes): o = cameraPos, d =
+ * normalize(viewportFront + viewportRight * x + viewportUp * y) with x =
+ * float(2 * px - width) / width and y likewise from the image row: main's
+ * basicShading branch (compute.glsl:665-676), evaluated as the preview
+ * evaluates it, so the bits are the preview's rays'.  tmax = 0 (unbounded)
+ * and pad = 0.  The jittered rays of the path tracer are not offered.  One
+ * small launch, asynchronous on `stream`; it reads nothing of the scene but
+ * its device and does not count in rt2_scene_stats.  Bad arguments (a null
+ * scene or uniforms, zero width or height, a bad shard, a null or misaligned
+ * d_rays for a non-empty slab) return < 0 before any device call.
+ * rt2_camera_rays_host is the blocking form into a host array.
+ * ---------------------------------------------------------------------- */
+typedef struct rt2_surface {          /* 48 B, three 16-B stores per ray */
+    float dst; int32_t tri; int32_t mtl; int32_t mtl_type;
+    float normal[3]; float u;
+    float albedo[3]; float v;
+} rt2_surface;
+
+int rt2_surface_rays(rt2_scene* scene, const rt2_ray* d_rays, int64_t n, rt2_surface* d_out, int flags, void* stream);
+int rt2_surface_rays_host(rt2_scene* scene, const rt2_ray* rays, int64_t n, rt2_surface* out, int flags);
+int rt2_camera_rays(rt2_scene* scene, const rt2_uniforms* uniforms, rt2_shard shard, rt2_ray* d_rays, void* stream);
+int rt2_camera_rays_host(rt2_scene* scene, const rt2_uniforms* uniforms, rt2_shard shard, rt2_ray* rays);
+
+/* ------------------------------------------------------------------------
  * (1b) Multi-GPU: row-tile shards + one RCCL gather
  *
  * The reference renders on one GPU and reads the framebuffer back with

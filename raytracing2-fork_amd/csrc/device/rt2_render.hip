@@ -45,6 +45,7 @@ using namespace rt2d;
 #include "rt2_misc_kernels.h"
 #include "rt2_query.h"
 #include "rt2_occluded.h"
+#include "rt2_surface.h"
 
 /* =========================================================================
  * C-ABI, device half
@@ -131,6 +132,10 @@ struct rt2_scene {
     uint8_t* d_occluded_out = nullptr;
     size_t occluded_cap = 0;          // rays the two buffers hold
     int occluded_arm = 0;             // experiment build: A/B arm of occluded_k5r
+    // rt2_surface_rays_host / rt2_camera_rays_host: staging buffers, kept like the above
+    rt2_ray* d_surface_rays = nullptr;
+    rt2_surface* d_surface_out = nullptr;
+    size_t surface_rays_cap = 0, surface_out_cap = 0;  // records each buffer holds
     unsigned long long* d_region_ctr = nullptr;  // 8 item-region counters, 128 B apart
     unsigned long long* wave_log = nullptr;  // diagnostic wave timeline (rt2_scene_set_wave_log)
     uint32_t wave_log_n = 0;
@@ -513,6 +518,8 @@ extern "C" void rt2_scene_destroy(rt2_scene* s) {
     (void)hipFree(s->d_query_hits);
     (void)hipFree(s->d_occluded_rays);
     (void)hipFree(s->d_occluded_out);
+    (void)hipFree(s->d_surface_rays);
+    (void)hipFree(s->d_surface_out);
     (void)hipFree(s->d_region_ctr);
     if (s->host_stream) (void)hipStreamDestroy(s->host_stream);
     delete s;
@@ -1523,6 +1530,191 @@ extern "C" int rt2_occluded_host(rt2_scene* s, const rt2_ray* rays, int64_t n, u
     HIPCHECK(hipMemcpyAsync(s->d_occluded_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
     if (rt2_occluded(s, s->d_occluded_rays, n, s->d_occluded_out, flags, st) != 0) return -1;
     HIPCHECK(hipMemcpyAsync(occluded, s->d_occluded_out, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+/* -------------------------------------------------------------------------
+ * Surface queries (rt2_surface.h)
+ * ----------------------------------------------------------------------- */
+namespace {
+// after the occlusion queries' codes: what rt2_scene_diag reports as the variant last launched
+enum : int { S_RES = -10, S_RES_L2 = -11, S_SCALAR = -12, S_BVH = -13 };
+
+// Grows one of the scene's two surface staging buffers to n records (the stream is drained first: the old
+// buffer may still be in use).
+template <class T>
+int surface_staging(rt2_scene* s, T*& buf, size_t& cap, size_t n) {
+    if (n <= cap) return 0;
+    HIPCHECK(hipStreamSynchronize(s->host_stream));
+    (void)hipFree(buf);
+    buf = nullptr;
+    cap = 0;
+    HIPCHECK(hipMalloc(&buf, n * sizeof(T)));
+    cap = n;
+    return 0;
+}
+}  // namespace
+
+extern "C" int rt2_surface_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, rt2_surface* d_out, int flags,
+                                void* stream) {
+    if (!s || n < 0 || (n > 0 && (!d_rays || !d_out)) || (flags & ~RT2_TRACE_SCALAR) ||
+        (reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15)) {
+        rt2h::set_error("rt2_surface_rays: bad argument (a scene, n >= 0, rays and records aligned to 16 B, flags 0 "
+                        "or RT2_TRACE_SCALAR)");
+        return -1;
+    }
+    if (n == 0) return 0;
+    const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
+    if (bvh && s->n_nodes == 0) {
+        rt2h::set_error("rt2_surface_rays: bad argument (BVH traversal needs the node array)");
+        return -1;
+    }
+    HIPCHECK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.tri = s->d_tri;
+    p.n_tris = s->n_tris;
+    p.mfma_A = s->mfma_A;
+    p.mfma_kt_frag = s->d_mfma_kt;
+    p.nodes = s->d_nodes;
+    p.stack_slots = s->bvh_depth + 2;
+    p.item_counter = s->d_counters;
+    p.seg_counter = s->d_counters + 1;
+    // what surface_record reads
+    p.unit_n = s->d_unit_n;
+    p.tri_mtl = s->d_mtl;
+    p.mats = s->d_mats;
+    p.n_mats = s->n_mats;
+    p.raw = s->d_raw;
+    p.texels = s->d_texels;
+    p.tex_desc = s->d_tex_desc;
+    p.n_tex = s->n_tex;
+    p.num_textures = std::min(s->n_tex, 5);  // a ray query has no uniforms: the images bound, at most the five units
+    SurfaceParams q{d_rays, d_out, (long long)n};
+    // the kernel choice of rt2_trace_rays
+    const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
+    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
+    if (matrix) {
+        const unsigned blocks = (unsigned)std::min<long long>(s->num_cus, (n + 1023) / 1024);
+        const bool resident = (s->n_tris + 31) / 32 <= kResGroups;
+        if (resident)
+            hipLaunchKernelGGL(surface_k5r<kQueryRes>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
+        else
+            hipLaunchKernelGGL(surface_k5r<kQueryResL2>, dim3(blocks), dim3(kQueryResL2.block), 0, st, p, q);
+        HIPCHECK(hipGetLastError());
+        s->last_kind = K_MFMA;
+        s->last_variant = resident ? S_RES : S_RES_L2;
+    } else {
+        for (long long i0 = 0; i0 < (long long)n; i0 += kQuerySlice) {
+            q.rays = d_rays + i0;
+            q.out = d_out + i0;
+            q.n = std::min<long long>(kQuerySlice, (long long)n - i0);
+            const unsigned blocks = (unsigned)((q.n + kQueryBlock - 1) / kQueryBlock);
+            if (bvh)
+                hipLaunchKernelGGL((surface_scalar<kQueryBlock, true>), dim3(blocks), dim3(kQueryBlock),
+                                   (size_t)p.stack_slots * kQueryBlock * sizeof(int), st, p, q);
+            else
+                hipLaunchKernelGGL((surface_scalar<kQueryBlock, false>), dim3(blocks), dim3(kQueryBlock), 0, st, p,
+                                   q);
+            HIPCHECK(hipGetLastError());
+        }
+        s->last_kind = bvh ? K_BVH : K_SMEM;
+        s->last_variant = bvh ? S_BVH : S_SCALAR;
+    }
+    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(s->last_launch, st));
+    s->last_launch_valid = true;
+    s->tests_per_seg = (unsigned long long)s->n_tris;
+    return 0;
+}
+
+extern "C" int rt2_surface_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n, rt2_surface* out, int flags) {
+    if (!s || n < 0 || (n > 0 && (!rays || !out)) || (flags & ~RT2_TRACE_SCALAR)) {
+        rt2h::set_error("rt2_surface_rays_host: bad argument (a scene, n >= 0, flags 0 or RT2_TRACE_SCALAR)");
+        return -1;
+    }
+    if (n == 0) return 0;
+    if (s->traversal == RT2_TRAVERSAL_BVH && s->n_nodes == 0) {
+        rt2h::set_error("rt2_surface_rays_host: bad argument (BVH traversal needs the node array)");
+        return -1;
+    }
+    HIPCHECK(hipSetDevice(s->device));
+    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    hipStream_t st = s->host_stream;
+    if (surface_staging(s, s->d_surface_rays, s->surface_rays_cap, (size_t)n) != 0) return -1;
+    if (surface_staging(s, s->d_surface_out, s->surface_out_cap, (size_t)n) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(s->d_surface_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
+    if (rt2_surface_rays(s, s->d_surface_rays, n, s->d_surface_out, flags, st) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(out, s->d_surface_out, (size_t)n * sizeof(rt2_surface), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// The argument checks of both camera-ray entry points; the slab's pixel count in *n.
+static int camera_rays_args(const char* who, const rt2_scene* s, const rt2_uniforms* u, rt2_shard sh,
+                            const void* rays, bool device, long long* n) {
+    const std::string w(who);
+    if (!s || !u) {
+        rt2h::set_error(w + ": bad argument (a scene and uniforms)");
+        return -1;
+    }
+    if (u->width < 1 || u->height < 1 || u->width > 0x3fffffffu || u->height > 0x3fffffffu) {
+        rt2h::set_error(w + ": bad argument (width and height must be in [1, 2^30))");
+        return -1;
+    }
+    const int rows = rt2_shard_rows((int)u->height, sh);
+    if (rows < 0) {
+        rt2h::set_error(w + ": bad argument (bad shard)");
+        return -1;
+    }
+    *n = (long long)rows * (long long)u->width;
+    if (*n > 0 && (!rays || (device && (reinterpret_cast<uintptr_t>(rays) & 15)))) {
+        rt2h::set_error(w + ": bad argument (rays must not be null" + (device ? ", and aligned to 16 B)" : ")"));
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" int rt2_camera_rays(rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, rt2_ray* d_rays, void* stream) {
+    long long n = 0;
+    if (camera_rays_args("rt2_camera_rays", s, u, sh, d_rays, true, &n) != 0) return -1;
+    if (n == 0) return 0;
+    HIPCHECK(hipSetDevice(s->device));
+    CameraParams c;
+    std::memset(&c, 0, sizeof(c));
+    auto cp = [](float* d, const rt2_vec4& v) {
+        d[0] = v.x;
+        d[1] = v.y;
+        d[2] = v.z;
+    };
+    cp(c.cam, u->cameraPos);
+    cp(c.vpRight, u->viewportRight);
+    cp(c.vpUp, u->viewportUp);
+    cp(c.vpFront, u->viewportFront);
+    c.W = (int)u->width;
+    c.H = (int)u->height;
+    c.tile_rows = sh.tile_rows;
+    c.rank = sh.rank;
+    c.nranks = sh.nranks;
+    c.n = n;
+    c.out = d_rays;
+    hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int rt2_camera_rays_host(rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, rt2_ray* rays) {
+    long long n = 0;
+    if (camera_rays_args("rt2_camera_rays_host", s, u, sh, rays, false, &n) != 0) return -1;
+    if (n == 0) return 0;
+    HIPCHECK(hipSetDevice(s->device));
+    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    hipStream_t st = s->host_stream;
+    if (surface_staging(s, s->d_surface_rays, s->surface_rays_cap, (size_t)n) != 0) return -1;
+    if (rt2_camera_rays(s, u, sh, s->d_surface_rays, st) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(rays, s->d_surface_rays, (size_t)n * sizeof(rt2_ray), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     return 0;
 }

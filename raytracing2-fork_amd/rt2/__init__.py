@@ -157,9 +157,15 @@ assert TRI_DTYPE.itemsize == 80 and MAT_DTYPE.itemsize == 96 and NODE_DTYPE.item
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("tmax", "<f4"), ("d", "<f4", 3), ("pad", "<f4")])
 HIT_DTYPE = np.dtype([("dst", "<f4"), ("tri", "<i4")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 8
+# rt2_surface (surface queries): the hit record of rt2_trace_rays, the material, the unit normal, the
+# barycentrics of b and c, and the base colour; a miss has tri = mtl = mtl_type = -1 and zeros
+SURFACE_DTYPE = np.dtype([("dst", "<f4"), ("tri", "<i4"), ("mtl", "<i4"), ("mtl_type", "<i4"), ("normal", "<f4", 3),
+                          ("u", "<f4"), ("albedo", "<f4", 3), ("v", "<f4")])
+assert SURFACE_DTYPE.itemsize == 48
 TRACE_AUTO, TRACE_SCALAR = 0, 1  # RT2_TRACE_AUTO, RT2_TRACE_SCALAR
 QUERY_RES, QUERY_RES_L2, QUERY_SCALAR, QUERY_BVH = -2, -3, -4, -5  # Scene.last_kernel after a query
 OCCLUDED_RES, OCCLUDED_RES_L2, OCCLUDED_SCALAR, OCCLUDED_BVH = -6, -7, -8, -9  # ... after an occlusion query
+SURFACE_RES, SURFACE_RES_L2, SURFACE_SCALAR, SURFACE_BVH = -10, -11, -12, -13  # ... after a surface query
 
 # Every symbol include/rt2.h declares (tests check the library exports them all).
 EXPORTED = [
@@ -177,6 +183,7 @@ EXPORTED = [
     "rt2_scene_set_textures", "rt2_comm_unique_id", "rt2_comm_init", "rt2_comm_wrap", "rt2_comm_destroy",
     "rt2_comm_size", "rt2_comm_check", "rt2_gather_slabs", "rt2_unshard_slabs", "rt2_render_host_gather",
     "rt2_comm_wait", "rt2_trace_rays", "rt2_trace_rays_host", "rt2_occluded", "rt2_occluded_host",
+    "rt2_surface_rays", "rt2_surface_rays_host", "rt2_camera_rays", "rt2_camera_rays_host",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -220,6 +227,10 @@ def lib() -> C.CDLL:
         "rt2_trace_rays_host": (C.c_int, [P, P, I64, P, C.c_int]),
         "rt2_occluded": (C.c_int, [P, P, I64, P, C.c_int, P]),
         "rt2_occluded_host": (C.c_int, [P, P, I64, P, C.c_int]),
+        "rt2_surface_rays": (C.c_int, [P, P, I64, P, C.c_int, P]),
+        "rt2_surface_rays_host": (C.c_int, [P, P, I64, P, C.c_int]),
+        "rt2_camera_rays": (C.c_int, [P, C.POINTER(Uniforms), Shard, P, P]),
+        "rt2_camera_rays_host": (C.c_int, [P, C.POINTER(Uniforms), Shard, P]),
         "rt2_resolve_rgba32f": (C.c_int, [P, I64, U32, P, P]),
         "rt2_resolve_rgb8_reference": (C.c_int, [P, I64, U32, P]),
         "rt2_scene_stats": (C.c_int, [P, C.POINTER(Stats), C.c_int]),
@@ -648,11 +659,87 @@ class Scene:
                                   C.c_void_p(out_ptr) if out_ptr else None, int(flags),
                                   C.c_void_p(stream) if stream else None), "rt2_occluded")
 
+    def surface(self, origins, directions, tmax=None, flags: int = 0) -> np.ndarray:
+        """What is at the closest hit of n rays (rt2_surface_rays_host, blocking):
+        the arguments of trace_rays; returns a SURFACE_DTYPE array of n records.
+        dst and tri are trace_rays' result; on a hit mtl and mtl_type are the
+        triangle's material index and type, normal the triangle's unit normal
+        (it faces the ray), u and v the barycentric weights of b and c, albedo
+        the surface's base colour (traceBasic with one bounce and no shadow).
+        A miss has tri = mtl = mtl_type = -1, dst = the ray's bound and zeros."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise RT2Error(f"surface: {len(o)} origins for {len(d)} directions")
+        rays = np.zeros(len(o), dtype=RAY_DTYPE)
+        rays["o"], rays["d"] = o, d
+        if tmax is not None:
+            rays["tmax"] = np.asarray(tmax, dtype=np.float32)
+        out = np.zeros(len(o), dtype=SURFACE_DTYPE)
+        _check(lib().rt2_surface_rays_host(self._p, rays.ctypes.data, len(rays), out.ctypes.data, int(flags)),
+               "rt2_surface_rays_host")
+        return out
+
+    def surface_device(self, rays_ptr: int, n: int, out_ptr: int, flags: int = 0, stream: int = 0) -> None:
+        """Asynchronous surface query over device arrays of n rt2_ray / rt2_surface records (rt2_surface_rays)."""
+        _check(lib().rt2_surface_rays(self._p, C.c_void_p(rays_ptr) if rays_ptr else None, int(n),
+                                      C.c_void_p(out_ptr) if out_ptr else None, int(flags),
+                                      C.c_void_p(stream) if stream else None), "rt2_surface_rays")
+
+    def camera_rays(self, u: Uniforms, sh: Optional[Shard] = None) -> np.ndarray:
+        """The deterministic primary ray of every pixel of the shard's slab
+        (rt2_camera_rays_host, blocking): a RAY_DTYPE array of rows * width
+        records in slab-row order, the preview's rays bit for bit."""
+        sh = sh or shard()
+        rows = shard_rows(u.height, sh)
+        rays = np.zeros(max(rows, 0) * u.width, dtype=RAY_DTYPE)
+        _check(lib().rt2_camera_rays_host(self._p, C.byref(u), sh, rays.ctypes.data), "rt2_camera_rays_host")
+        return rays
+
+    def camera_rays_device(self, u: Uniforms, sh: Shard, rays_ptr: int, stream: int = 0) -> None:
+        """Asynchronous: the slab's primary rays into a device array of rt2_ray records (rt2_camera_rays)."""
+        _check(lib().rt2_camera_rays(self._p, C.byref(u), sh, C.c_void_p(rays_ptr) if rays_ptr else None,
+                                     C.c_void_p(stream) if stream else None), "rt2_camera_rays")
+
+    def feature_buffers(self, u: Uniforms, sh: Optional[Shard] = None, flags: int = 0) -> dict:
+        """First-hit feature buffers of a view, for a denoiser, picking or
+        masks: the slab's camera rays are written into a device buffer and
+        their surface records follow on the same stream.  Returns slab-shaped
+        arrays: depth [rows, W] (1e38 where nothing is hit), tri, mtl and
+        mtl_type [rows, W] (-1 where nothing is hit), normal and albedo
+        [rows, W, 3], uv [rows, W, 2].  u.numTextures is not consulted: a
+        surface query takes the number of images given to set_textures."""
+        import torch
+
+        sh = sh or shard()
+        rows = shard_rows(u.height, sh)
+        if rows < 0:
+            raise RT2Error("feature_buffers: bad shard")
+        W = int(u.width)
+        n = rows * W
+        rec = np.zeros(n, dtype=SURFACE_DTYPE)
+        if n:
+            dev = torch.device("cuda", self.device)
+            with torch.cuda.device(dev):
+                rays = torch.empty(n * RAY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                out = torch.empty(n * SURFACE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                self.camera_rays_device(u, sh, rays.data_ptr(), stream)
+                self.surface_device(rays.data_ptr(), n, out.data_ptr(), flags, stream)
+                rec = out.cpu().numpy().view(SURFACE_DTYPE)  # the copy waits for the stream
+        shape = (rows, W)
+        return {"depth": rec["dst"].reshape(shape).copy(), "tri": rec["tri"].reshape(shape).copy(),
+                "mtl": rec["mtl"].reshape(shape).copy(), "mtl_type": rec["mtl_type"].reshape(shape).copy(),
+                "normal": rec["normal"].reshape(shape + (3,)).copy(),
+                "albedo": rec["albedo"].reshape(shape + (3,)).copy(),
+                "uv": np.stack([rec["u"], rec["v"]], -1).reshape(shape + (2,))}
+
     def last_kernel(self) -> int:
         """What the scene launched last (rt2_scene_diag): a render's variant id (-1: the traceBasic preview), or
         after a query QUERY_RES (trace_rays_k5r, every group resident), QUERY_RES_L2 (its L2 continuation),
         QUERY_SCALAR or QUERY_BVH (trace_rays_scalar); after an occlusion query OCCLUDED_RES, OCCLUDED_RES_L2
-        (occluded_k5r), OCCLUDED_SCALAR or OCCLUDED_BVH (occluded_scalar)."""
+        (occluded_k5r), OCCLUDED_SCALAR or OCCLUDED_BVH (occluded_scalar); after a surface query SURFACE_RES,
+        SURFACE_RES_L2 (surface_k5r), SURFACE_SCALAR or SURFACE_BVH (surface_scalar)."""
         c, v = (C.c_ulonglong * 8)(), C.c_int(-1)
         if lib().rt2_scene_diag(self._p, c, C.byref(v)) != 0:
             raise RT2Error("rt2_scene_diag failed")

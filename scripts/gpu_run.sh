@@ -19,6 +19,8 @@
 #   OCC_AB=<rounds>  occlusion-query A/B against rt2_trace_rays, every arm of the experiment build
 #                    (scripts/occluded_ab.py; needs rt2/librt2_exp.so): rewrites profiles/occluded_ab.json;
 #                    OCC_AB_OUT=<file> writes there instead
+#   SURFACE_AB=<rounds>  surface-query A/B against rt2_trace_rays and the scalar kernel (scripts/surface_ab.py):
+#                    rewrites profiles/surface_ab.json; SURFACE_AB_OUT=<file> writes there instead
 #   TAG=<name>       suffix of the output files
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
@@ -64,6 +66,11 @@ if [ -n "${OCC_AB}" ]; then
   timeout -k 10 1100 python -u scripts/occluded_ab.py --rounds "${OCC_AB}" ${OCC_AB_OUT:+--out "$OCC_AB_OUT"} \
     || { echo "occlusion-query A/B failed"; exit 1; }
   echo "occlusion-query A/B ok"
+fi
+if [ -n "${SURFACE_AB}" ]; then
+  timeout -k 10 600 python -u scripts/surface_ab.py --rounds "${SURFACE_AB}" ${SURFACE_AB_OUT:+--out "$SURFACE_AB_OUT"} \
+    || { echo "surface-query A/B failed"; exit 1; }
+  echo "surface-query A/B ok"
 fi
 if [ -n "${BENCH}" ]; then
   bargs="${BENCH}"; [ "${BENCH}" = default ] && bargs="--full"
