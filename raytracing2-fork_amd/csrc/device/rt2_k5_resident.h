@@ -70,6 +70,16 @@
 // own T1 piece, written once per pixel-frame and read once per ray
 // (render_mfma_k5r; rt2_path.h advance<.., PARK>).  Neither changes a value
 // that reaches the image.
+//
+// MfmaSpec::cluster_rows (353, 354): the scene's groups come in clusters
+// (rt2_cluster.h; the table lies behind the kt records), and a compact
+// cluster's groups are swept only for the rays whose half line can meet its
+// padded box: skipped when no live ray does, and in the one-block form, at
+// half the products and half the fold, with those rays moved into one 32-row
+// fragment when at most 32 do (sweep_kt_res, cluster_rows_frag).  The hot
+// masks can only lose triangles no ray of the wave can hit; the episode builds
+// every ray's pass mask from the unpermuted fragments as before (DESIGN.md
+// "Compact clusters").
 #pragma once
 
 // v_writelane_b32 (value and lane wave-uniform).  clang has a builtin for
@@ -365,9 +375,51 @@ __device__ __forceinline__ void phase_prio(int phase) {  // 0 products, 1 exact 
 // groups [kResGroups, ng) are read from the scene's kt records in L2 after the
 // resident ones, in the same (index) order.  Returns false (wave-uniform,
 // nothing computed) when a ray is outside the filter's range.
+// MfmaSpec::cluster_rows, diag: per (wave, compact cluster) of a sweep, the
+// three cases and the rays that needed the cluster
+struct ClusterDiag {
+    unsigned long long skipped = 0, one = 0, two = 0, rays = 0;
+};
+
+// MfmaSpec::cluster_rows.  One 32-row fragment out of a0[0] / a0[1] that holds
+// the rays of `need` (at most 32 of them) in its rows 0 .. c - 1; the other
+// rows hold other rays of the wave (every row of a0 is a valid ray: lanes
+// without one carry a live lane's).  Each block's 32 rows are permuted as a
+// whole, its needing rows to the front (block 0's to row 0, block 1's behind
+// them) and the rest behind those, cyclically, so every ds_permute is a
+// permutation of the 64 lanes; a row below c0 is then taken from block 0's
+// result and every other one from block 1's.  Rank by mbcnt, one
+// v_permlane32_swap to hand a ray's row to the two lanes that hold its
+// k-slots, 8 ds_permute, 4 selects; no LDS.
+__device__ __forceinline__ h8 cluster_rows_frag(const h8* a0, unsigned long long need) {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const int l = (int)lane_id();
+    const int c0 = __popc((uint32_t)need), c1 = __popc((uint32_t)(need >> 32));
+    const int rk = (int)lanes_below(need);
+    const bool nb = (need >> l) & 1ull;
+    // rows of this lane's own ray: block 0 (l < 32) and block 1
+    const int rest = ((l - rk) + (l < 32 ? c0 : c1 + 2 * c0)) & 31;
+    const uint32_t row = (uint32_t)(nb ? rk : rest);
+    // sw[0]: lanes l and l + 32 both hold the row of ray l (block 0's layout); sw[1]: of ray l + 32
+    const auto sw = __builtin_amdgcn_permlane32_swap(row, row, false, false);
+    const int half = l & 32;
+    const int to0 = 4 * ((int)sw[0] + half), to1 = 4 * ((int)sw[1] + half);
+    const u4 b0 = __builtin_bit_cast(u4, a0[0]), b1 = __builtin_bit_cast(u4, a0[1]);
+    const bool first = (l & 31) < c0;
+    u4 r;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int x0 = __builtin_amdgcn_ds_permute(to0, (int)b0[k]);
+        const int x1 = __builtin_amdgcn_ds_permute(to1, (int)b1[k]);
+        r[k] = (uint32_t)(first ? x0 : x1);
+    }
+    return __builtin_bit_cast(h8, r);
+}
+
 template <MfmaSpec S>
 __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* rec, const f3& o, const f3& d,
-                                             float& best, int& bi, float& bestK, MfmaDiag& dg, bool upper) {
+                                             float& best, int& bi, float& bestK, MfmaDiag& dg, bool upper,
+                                             unsigned long long act = 0, ClusterDiag* cd = nullptr) {
     const int lane = (int)lane_id();
     // MfmaSpec::diag: shader clocks of the ray setup (t_wait), the products
     // with their record reads (t_filt), the exact phase with the Y rebuilds
@@ -440,24 +492,131 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
                 // wave-uniform, so one v_writelane puts the mask into lane j
                 // (the loop below pays a v_mov, a compare and a select).
                 // kt_group keeps its own basic blocks and scheduling groups.
-                auto group = [&](const h8* t, int j) {
+                auto group = [&](const h8* t, int j, bool up) {
                     const h8 b0 = t[0], b1 = t[64], b2 = t[128];
                     h8 b3 = {};
                     if constexpr (YP) b3 = t[192];
-                    const unsigned long long M = kt_group<YP>(a0, y1, b0, b1, b2, b3, upper);
+                    const unsigned long long M = kt_group<YP>(a0, y1, b0, b1, b2, b3, up);
                     const uint32_t m32 = (uint32_t)(M | M >> 32);
                     maskv = rt2_writelane((int)m32, j, maskv);
                     any |= m32;
                 };
-                int j = 0;
-                for (; j + 1 < cnt; j += 2) {
-                    group(tb, j);
-                    group(tb + kKtOps * 64, j + 1);
-                    tb += 2 * kKtOps * 64;
+                // groups [j, j1) in the two-block form, two per trip
+                auto two_block = [&](int j, int j1, bool up) {
+                    for (; j + 1 < j1; j += 2) {
+                        group(tb, j, up);
+                        group(tb + kKtOps * 64, j + 1, up);
+                        tb += 2 * kKtOps * 64;
+                    }
+                    if (j < j1) {
+                        group(tb, j, up);
+                        tb += kKtOps * 64;
+                    }
+                };
+                bool clustered = false;
+                [[maybe_unused]] cfloat* ct = nullptr;  // the scene's rt2_cluster_table, behind the records
+                // (a window with Y is instantiated but never run in these kernels)
+                if constexpr (S.cluster_rows && !YP) {
+                    static_assert(!S.res_l2 && W >= kResGroups && !S.y_first,
+                                  "cluster_rows: one window of every group, no distance bound in it");
+                    ct = (cfloat*)(reinterpret_cast<const h8*>(p.mfma_kt_frag) + (size_t)ng * (kKtOps * 64));
+                    clustered = __float_as_int(ct[1]) != 0;
                 }
-                if (j < cnt) {
-                    group(tb, j);
-                    tb += kKtOps * 64;
+                if (!clustered) two_block(0, cnt, upper);
+                if constexpr (S.cluster_rows && !YP) {
+                    if (clustered) {
+                        // MfmaSpec::cluster_rows (DESIGN.md "Compact clusters").
+                        // The need test, once per sweep: for every compact
+                        // cluster the live rays (act) whose half line can meet
+                        // its padded box (rt2_cluster.h; the bounds by scalar
+                        // loads), parked in lanes kNeedLane + 2 k and + 1 of
+                        // maskv, which the at most kResGroups hot masks leave
+                        // free (no VGPR added; cleared again before the
+                        // episode); the reciprocals die with this block.
+                        const int ncl = __float_as_int(ct[1]);
+                        const float far_o = ct[0];
+                        ct += 8;  // the entries
+                        constexpr int kNeedLane = 64 - 2 * RT2_MAX_CLUSTERS;
+                        static_assert(kNeedLane >= kResGroups, "the need masks share maskv with the hot masks");
+                        {
+                            const float of[3] = {o.x, o.y, o.z}, df[3] = {d.x, d.y, d.z};
+                            float inv[3];
+                            rt2_cluster_inv(df, inv);
+                            const bool always = rt2_cluster_always(of, df, far_o);
+#pragma nounroll
+                            for (int k = 0; k < ncl; k++) {
+                                const float4 c0 = ldc4(ct + 8 * k), c1 = ldc4(ct + 8 * k + 4);
+                                unsigned long long nm = act;
+                                if (__float_as_int(c1.w) & RT2_CLUSTER_COMPACT) {
+                                    const float lo[3] = {c0.x, c0.y, c0.z}, hi[3] = {c1.x, c1.y, c1.z};
+                                    nm &= __ballot(always || rt2_cluster_need_box(lo, hi, of, inv));
+                                }
+                                maskv = rt2_writelane((int)(uint32_t)nm, kNeedLane + 2 * k, maskv);
+                                maskv = rt2_writelane((int)(uint32_t)(nm >> 32), kNeedLane + 2 * k + 1, maskv);
+                            }
+                        }
+                        // groups [j, j1) in the one-block form with fragment af, two per trip
+                        auto one_block = [&](const h8& af, int j, int j1) {
+                            for (; j + 1 < j1; j += 2) {
+                                const h8* t = tb;
+                                unsigned long long M0, M1;
+                                kt_group_one2(af, t[0], t[64], t[128], t[kKtOps * 64], t[kKtOps * 64 + 64],
+                                              t[kKtOps * 64 + 128], M0, M1);
+                                const uint32_t m0 = (uint32_t)(M0 | M0 >> 32), m1 = (uint32_t)(M1 | M1 >> 32);
+                                maskv = rt2_writelane((int)m0, j, maskv);
+                                maskv = rt2_writelane((int)m1, j + 1, maskv);
+                                any |= m0 | m1;
+                                tb += 2 * kKtOps * 64;
+                            }
+                            if (j < j1) {
+                                const h8 b0 = tb[0], b1 = tb[64], b2 = tb[128], b3 = {};
+                                const unsigned long long M = kt_group<false>(&af, y1, b0, b1, b2, b3, false);
+                                const uint32_t m32 = (uint32_t)(M | M >> 32);
+                                maskv = rt2_writelane((int)m32, j, maskv);
+                                any |= m32;
+                                tb += kKtOps * 64;
+                            }
+                        };
+#pragma nounroll
+                        for (int k = 0; k < ncl; k++) {
+                            const int g0 = __float_as_int(ct[8 * k + 3]), gf = __float_as_int(ct[8 * k + 7]);
+                            const int g1 = gf & 0xffff;
+                            const unsigned long long need =
+                                (unsigned long long)(uint32_t)__builtin_amdgcn_readlane(maskv, kNeedLane + 2 * k) |
+                                (unsigned long long)(uint32_t)__builtin_amdgcn_readlane(maskv, kNeedLane + 2 * k + 1) << 32;
+                            const int c = __popcll(need);
+                            const bool compact = (gf & RT2_CLUSTER_COMPACT) != 0;
+                            if constexpr (S.diag)
+                                if (compact) {
+                                    cd->rays += (unsigned long long)c;
+                                    if (!c)
+                                        cd->skipped += 1;
+                                    else if (!upper || c <= 32)
+                                        cd->one += 1;
+                                    else
+                                        cd->two += 1;
+                                }
+                            if (!c) {  // no live ray can meet the box: the groups' hot masks stay 0
+                                tb += (g1 - g0) * (kKtOps * 64);
+                                continue;
+                            }
+                            if (upper && !(compact && c <= 32)) {
+                                // `upper` is true here, but kt_group is to keep the branch on it: folded
+                                // away, a group's products and its fold share a basic block with their
+                                // neighbours, the scheduling groups no longer hold and the products take 96
+                                // registers instead of 48
+                                int up = 1;
+                                asm volatile("" : "+s"(up));
+                                two_block(g0, g1, up != 0);
+                            } else {
+                                // a wave of at most 32 live rays has them in block 0 already
+                                h8 af = a0[0];
+                                if (upper) af = cluster_rows_frag(a0, need);
+                                one_block(af, g0, g1);
+                            }
+                        }
+                        maskv = lane < kNeedLane ? maskv : 0;  // the episode reads every lane as a hot mask
+                    }
                 }
             } else {
                 for (int j = 0; j < cnt; j++) {
@@ -586,6 +745,8 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
     Lane L;
     lane_init(L);
     MfmaDiag dg;
+    struct NoClusterDiag {};
+    [[maybe_unused]] std::conditional_t<S.cluster_rows, ClusterDiag, NoClusterDiag> cdg;
     [[maybe_unused]] PathDiagSlot<S.diag> pds;
     const int wave = (int)(threadIdx.x >> 6);
     // MfmaSpec::lean: the wave counts its lanes' segments (no per-lane counter)
@@ -702,7 +863,11 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
         float best = 1e38f, bestK = 1e38f * 1.0009765625f;
         int bi = -1;
         phase_prio<S>(0);
-        const bool swept = sweep_kt_res<S>(p, rs.rec, ro, rd, best, bi, bestK, dg, upper);
+        bool swept;
+        if constexpr (S.cluster_rows)
+            swept = sweep_kt_res<S>(p, rs.rec, ro, rd, best, bi, bestK, dg, upper, act, &cdg);
+        else
+            swept = sweep_kt_res<S>(p, rs.rec, ro, rd, best, bi, bestK, dg, upper);
         // a ray outside the filter's range (wave-uniform): the drain's code
         if (!swept) coop_each(act, ro, rd, p, best, bi);
         phase_prio<S>(2);
@@ -771,6 +936,12 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
             atomicMax(p.seg_counter + 10, dg.xl[3]);    // the largest count of one ray in any episode
             atomicAdd(p.seg_counter + 22, pds.d.new_ray);  // PathDiag: advance's new-ray block, executions
             atomicAdd(p.seg_counter + 23, pds.d.new_px);   // ... its new-frame block
+            if constexpr (S.cluster_rows) {  // ClusterDiag: (wave, compact cluster) cases of the sweeps
+                atomicAdd(p.seg_counter + 24, cdg.skipped);  // ... no ray needs it
+                atomicAdd(p.seg_counter + 25, cdg.one);      // ... swept in the one-block form
+                atomicAdd(p.seg_counter + 26, cdg.two);      // ... more than 32 rays need it: two blocks
+                atomicAdd(p.seg_counter + 27, cdg.rays);     // ... the rays that need it, summed
+            }
         }
 }
 

@@ -73,6 +73,10 @@ struct MfmaSpec {
     bool cam_park = false;   // render_mfma_k5r without the T1 pieces (no_t1): a pixel's camera end point is computed
                              // once per pixel-frame and parked in the lane's 16 bytes of the wave's own unused T1
                              // piece; a new ray reads it back (rt2_path.h advance<.., PARK>)
+    bool cluster_rows = false;  // render_mfma_k5r, one window of every group: the scene's cluster table (rt2_cluster.h)
+                                // is followed: a compact cluster no live ray needs is skipped, one that at most 32
+                                // need is swept in the one-block form with those rays moved into one fragment
+                                // (rt2_k5_resident.h sweep_kt_res; DESIGN.md "Compact clusters")
 };
 
 // per-wave diagnostic counts (wave-uniform; MfmaSpec::diag)
@@ -643,6 +647,42 @@ __device__ __forceinline__ unsigned long long kt_group(const h8* a0, const h8* y
         acc = fold(t0, Y0, acc);
     }
     return __ballot(acc < 0);
+}
+
+// MfmaSpec::cluster_rows.  Two groups' filters for ONE 32-ray block `a` (the
+// form without Y): the two groups take the places kt_group gives the two
+// blocks, so a wave's products still run beside its own fold, at the same
+// peak of 48 product registers: [U0 V0 X0] [AND0] [U1] [or0] [V1 X1] [AND1]
+// [or1], with an accumulator and a ballot per group.
+__device__ __forceinline__ void kt_group_one2(const h8& a, const h8& bu0, const h8& bv0, const h8& bx0, const h8& bu1,
+                                              const h8& bv1, const h8& bx1, unsigned long long& M0,
+                                              unsigned long long& M1) {
+    const f16v zero = {};
+    int t0[16], t1[16], acc0 = 0, acc1 = 0;
+    const f16v U0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bu0, zero, 0, 0, 0);
+    const f16v V0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bv0, zero, 0, 0, 0);
+    const f16v X0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bx0, zero, 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 16; i++)
+        t0[i] = __builtin_amdgcn_bitop3_b32(__float_as_int(U0[i]), __float_as_int(V0[i]), __float_as_int(X0[i]), 0x80);
+    const f16v U1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bu1, zero, 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 8; i++) acc0 = __builtin_amdgcn_bitop3_b32(t0[2 * i], t0[2 * i + 1], acc0, 0xFE);
+    const f16v V1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bv1, zero, 0, 0, 0);
+    const f16v X1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bx1, zero, 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 16; i++)
+        t1[i] = __builtin_amdgcn_bitop3_b32(__float_as_int(U1[i]), __float_as_int(V1[i]), __float_as_int(X1[i]), 0x80);
+#pragma unroll
+    for (int i = 0; i < 8; i++) acc1 = __builtin_amdgcn_bitop3_b32(t1[2 * i], t1[2 * i + 1], acc1, 0xFE);
+    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);   // MFMA
+    __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);  // VALU
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+    __builtin_amdgcn_sched_group_barrier(0x002, 24, 0);
+    M0 = __ballot(acc0 < 0);
+    M1 = __ballot(acc1 < 0);
 }
 
 // Closest hit of every lane's ray (o, d) over all triangles, records read

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../../include/rt2.h"
+#include "../../../include/rt2_cluster.h"
 #include "rt2_math.h"
 
 using namespace rt2d;
@@ -85,6 +86,7 @@ struct rt2_scene {
     float2* d_mfma_k16_bnd = nullptr;           // per-triangle m.z residual bounds of the 5-product form (k5)
     _Float16* d_mfma_kt = nullptr;              // kthr records (threshold in the K-slots: 4 KiB per 32 triangles)
     int mfma_ok = 0;                            // render_mfma usable (records built, scene in range)
+    rt2_cluster_table clusters = {};            // MfmaSpec::cluster_rows: the groups' clusters (n = 0: none compact)
     float mfma_A = 0.0f;                        // max |a_i| over the in-range triangles
     float4* d_fb = nullptr;                     // frame_split scratch (per-frame colours)
     uchar4* d_texels = nullptr;                 // textures, RGBA8
@@ -454,7 +456,13 @@ static int scene_init(rt2_scene* s, const rt2_triangle* tris, int32_t n_tris, co
         s->mfma_ok = s->mfma_A <= 0x1p20f;
         // the kthr records (rt2_mfma.h prep_mfma_kt: the threshold in the
         // K-slots), 4 KiB per 32 triangles; its flags duplicate the above
-        HIPCHECK(hipMalloc(&s->d_mfma_kt, (size_t)n_pad32 * kKtOps * 16 * sizeof(_Float16)));
+        // ... and behind them the cluster table of a scene the resident kernel holds whole (MfmaSpec::cluster_rows;
+        // rt2_cluster.h), n = 0 for every other scene
+        const size_t kt_bytes = (size_t)n_pad32 * kKtOps * 16 * sizeof(_Float16);
+        if (n_pad32 / 32 <= kResGroups && rt2_cluster_table_build(tris, n_tris, &s->clusters) < 0) return -1;
+        HIPCHECK(hipMalloc(&s->d_mfma_kt, kt_bytes + sizeof(s->clusters)));
+        HIPCHECK(hipMemcpy(reinterpret_cast<char*>(s->d_mfma_kt) + kt_bytes, &s->clusters, sizeof(s->clusters),
+                           hipMemcpyHostToDevice));
         hipLaunchKernelGGL(prep_mfma_kt, dim3((n_pad32 + 255) / 256), dim3(256), 0, 0, s->d_tri, n_tris, n_pad32,
                            s->d_mfma_kt, d_mflags);
         HIPCHECK(hipGetLastError());
@@ -620,6 +628,12 @@ constexpr MfmaSpec kt_park(MfmaSpec x) {
     x.cam_park = true;
     return x;
 }
+// ... following the scene's cluster table: compact clusters swept with only the rays that need them
+// (MfmaSpec::cluster_rows; DESIGN.md "Compact clusters")
+constexpr MfmaSpec kt_cr(MfmaSpec x) {
+    x.cluster_rows = true;
+    return x;
+}
 constexpr int kResWin = 38;  // the window of 353-356 (and the diagnostic 350): the whole resident sweep, then one episode
 constexpr int kResL2Groups = 256;  // render_mfma_k5r with res_l2: kResGroups groups resident, the rest from L2
 // records streamed through LDS tiles (rt2_k5_tiles.h): 19-group tiles, each ray's own W, issue priority by
@@ -666,8 +680,8 @@ constexpr Variant kVariants[] = {
     // (DESIGN.md "Exact tests per ray"), two groups per trip of the products' loop with the hot masks by v_writelane
     // (DESIGN.md "Two groups per loop trip") and keep each pixel's camera end point in LDS instead of recomputing it
     // per ray (DESIGN.md "The camera end point once per pixel")
-    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
-    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
+    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_cr(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
+    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_cr(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
     RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, true, 4), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
     RT2_VARIANT(356, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, true, true), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw", kResL2Groups),
     // the default above 8,192 triangles: the LDS-tiled kernel (rt2_k5_tiles.h; 19-group tiles, fragments in
@@ -718,6 +732,11 @@ constexpr Variant kVariants[] = {
     RT2_VARIANT(406, K_MFMA, render_mfma_k5r<kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/nopark", kResGroups),
     RT2_VARIANT(407, K_MFMA, render_mfma_k5r<kt_park(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/nopair", kResGroups),
     RT2_VARIANT(408, K_MFMA, render_mfma_k5r<kt_xl(kt_win(kt_res(false, true, true), kResWin))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/nopair/nopark", kResGroups),
+    // the cluster table followed (MfmaSpec::cluster_rows; 353 / 354 take it): 353's and 354's specs without it (nocr:
+    // the form before), and the diagnostic build that counts the skipped / one-block / two-block cases
+    RT2_VARIANT(409, K_MFMA, render_mfma_k5r<kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/nocr", kResGroups),
+    RT2_VARIANT(410, K_MFMA, render_mfma_k5r<kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/nocr", kResGroups),
+    RT2_VARIANT(411, K_MFMA, render_mfma_k5r<kt_cr(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 0, true), kResWin))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/xl/cr", kResGroups),
     // the tile stream at 3 waves per SIMD (380 takes 4 with the lean lane state): with its diagnostic clocks; without
     // flow_prio; with the lean lane state
     RT2_VARIANT(370, K_MFMA, render_mfma_k5t<kt_tiles_flow()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp"),
@@ -1813,7 +1832,8 @@ extern "C" int rt2_device_selftest(const float* in, int32_t n, float* out10) {
 // host memory: 0 = pre-transformed triangles (3 float4 each), 1 = the filter
 // records in the 16x16x32 layout, 2 = their per-triangle tau, 3 = sweep_k16 records,
 // 4 = their tau, 5 = the k5 form's per-triangle m.z residual bounds, 6 = the
-// kthr records (threshold in the K-slots).  Returns the array's size in bytes (nothing copied when
+// kthr records (threshold in the K-slots), 7 = the cluster table (rt2_cluster_table of rt2_cluster.h, the host's
+// copy; n = 0 when the scene has no compact cluster).  Returns the array's size in bytes (nothing copied when
 // `host` is null or `bytes` is too small), < 0 on error.
 extern "C" long long rt2_scene_export(rt2_scene* s, int what, void* host, unsigned long long bytes) {
     if (!s) return -1;
@@ -1822,6 +1842,10 @@ extern "C" long long rt2_scene_export(rt2_scene* s, int what, void* host, unsign
     const void* src = nullptr;
     size_t sz = 0;
     if ((what == 1 || what == 2) && ensure_mfma16(s) != 0) return -1;
+    if (what == 7) {
+        if (host && bytes >= sizeof(s->clusters)) std::memcpy(host, &s->clusters, sizeof(s->clusters));
+        return (long long)sizeof(s->clusters);
+    }
     switch (what) {
     case 0: src = s->d_tri, sz = n * 3 * sizeof(float4); break;
     case 1: src = s->d_mfma, sz = n16 * kMfmaQ * 32 * sizeof(_Float16); break;
@@ -1839,6 +1863,36 @@ extern "C" long long rt2_scene_export(rt2_scene* s, int what, void* host, unsign
         HIPCHECK(hipMemcpy(host, src, sz, hipMemcpyDeviceToHost));
     }
     return (long long)sz;
+}
+
+// Not in rt2.h (test hook): replaces the scene's cluster table (rt2_cluster.h) by the caller's, for tests that
+// need clusters the upload rule would not choose.  The ranges must be contiguous and cover the scene's groups (the
+// kernel steps through the resident records by them); that every triangle lies inside its cluster's box is the
+// caller's business: a box that leaves one out loses hits, nothing else.  n = 0 switches the clusters off.
+extern "C" int rt2_scene_set_clusters(rt2_scene* s, const rt2_cluster_table* t) {
+    if (!s || !t || !s->d_mfma_kt) {
+        rt2h::set_error("rt2_scene_set_clusters: bad argument (a scene with matrix-filter records)");
+        return -1;
+    }
+    const int ng = (s->n_tris + 31) / 32;
+    bool ok = t->n >= 0 && t->n <= RT2_MAX_CLUSTERS && (t->n == 0 || ng <= kResGroups) && t->far_o >= 0.0f;
+    int g = 0;
+    for (int k = 0; ok && k < t->n; k++) {
+        const int g1 = t->c[k].g1_flags & 0xffff;
+        ok = t->c[k].g0 == g && g1 > g && (t->c[k].g1_flags & ~(0xffff | RT2_CLUSTER_COMPACT)) == 0;
+        g = g1;
+    }
+    if (!ok || (t->n > 0 && g != ng)) {
+        rt2h::set_error("rt2_scene_set_clusters: the ranges must be contiguous and cover the scene's groups");
+        return -1;
+    }
+    HIPCHECK(hipSetDevice(s->device));
+    HIPCHECK(hipDeviceSynchronize());
+    s->clusters = *t;
+    const size_t kt_bytes = (size_t)ng * 32 * kKtOps * 16 * sizeof(_Float16);
+    HIPCHECK(hipMemcpy(reinterpret_cast<char*>(s->d_mfma_kt) + kt_bytes, &s->clusters, sizeof(s->clusters),
+                       hipMemcpyHostToDevice));
+    return 0;
 }
 
 // Not in rt2.h (test hook): the matrix filter's terms on the hardware

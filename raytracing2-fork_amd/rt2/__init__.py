@@ -163,6 +163,12 @@ SURFACE_DTYPE = np.dtype([("dst", "<f4"), ("tri", "<i4"), ("mtl", "<i4"), ("mtl_
                           ("u", "<f4"), ("albedo", "<f4", 3), ("v", "<f4")])
 assert SURFACE_DTYPE.itemsize == 48
 TRACE_AUTO, TRACE_SCALAR = 0, 1  # RT2_TRACE_AUTO, RT2_TRACE_SCALAR
+# rt2_cluster / rt2_cluster_table (include/rt2_cluster.h): the resident kernel's clusters of triangle groups
+MAX_CLUSTERS, CLUSTER_COMPACT = 13, 0x10000
+CLUSTER_DTYPE = np.dtype([("lo", "<f4", 3), ("g0", "<i4"), ("hi", "<f4", 3), ("g1_flags", "<i4")])
+CLUSTER_TABLE_DTYPE = np.dtype([("far_o", "<f4"), ("n", "<i4"), ("pad_abs", "<f4"), ("reserved", "<i4", 5),
+                                ("c", CLUSTER_DTYPE, MAX_CLUSTERS)])
+assert CLUSTER_DTYPE.itemsize == 32 and CLUSTER_TABLE_DTYPE.itemsize == 32 + 32 * MAX_CLUSTERS
 QUERY_RES, QUERY_RES_L2, QUERY_SCALAR, QUERY_BVH = -2, -3, -4, -5  # Scene.last_kernel after a query
 OCCLUDED_RES, OCCLUDED_RES_L2, OCCLUDED_SCALAR, OCCLUDED_BVH = -6, -7, -8, -9  # ... after an occlusion query
 SURFACE_RES, SURFACE_RES_L2, SURFACE_SCALAR, SURFACE_BVH = -10, -11, -12, -13  # ... after a surface query
@@ -293,6 +299,9 @@ def lib() -> C.CDLL:
         "rt2_scene_plk_info": (C.c_int, [P, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
         "rt2_scene_export": (C.c_longlong, [P, C.c_int, P, C.c_ulonglong]),
         "rt2_mfma_probe": (C.c_int, [P, C.c_int, P, I32, P, P, P, P]),
+        "rt2_cluster_table_build": (C.c_int, [P, I32, P]),
+        "rt2_cluster_need": (C.c_int, [P, P, I64, P]),
+        "rt2_scene_set_clusters": (C.c_int, [P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -749,7 +758,7 @@ class Scene:
         """A derived device array of the scene (rt2_scene_export, test hook): 0 =
         pre-transformed triangles, 1/2 = render_mfma records/tau, 3/4 = sweep_k16 records/tau,
         5 = the k5 form's per-triangle m.z residual bounds (float32 pairs), 6 = the kthr records (threshold in
-        the K-slots)."""
+        the K-slots), 7 = the cluster table (one CLUSTER_TABLE_DTYPE record)."""
         n = lib().rt2_scene_export(self._p, what, None, 0)
         if n < 0:
             raise RT2Error("rt2_scene_export: bad argument")
@@ -757,6 +766,16 @@ class Scene:
         if n and lib().rt2_scene_export(self._p, what, out.ctypes.data, n) != n:
             raise RT2Error("rt2_scene_export failed")
         return out
+
+    def cluster_table(self) -> np.ndarray:
+        """The scene's cluster table (rt2_scene_export selector 7): one CLUSTER_TABLE_DTYPE record."""
+        return self.export(7, CLUSTER_TABLE_DTYPE)[0]
+
+    def set_cluster_table(self, table) -> None:
+        """Replaces the scene's cluster table (rt2_scene_set_clusters, test hook)."""
+        t = np.zeros(1, dtype=CLUSTER_TABLE_DTYPE)
+        t[0] = table
+        _check(lib().rt2_scene_set_clusters(self._p, t.ctypes.data), "rt2_scene_set_clusters")
 
     def mfma_probe(self, layout: int, rays: np.ndarray):
         """The matrix filter's terms on the device (rt2_mfma_probe, test hook):
@@ -798,6 +817,29 @@ class Scene:
         s = Stats()
         _check(lib().rt2_scene_stats(self._p, C.byref(s), int(reset)), "stats")
         return s
+
+
+def cluster_table(triangles: np.ndarray) -> np.ndarray:
+    """The cluster table rt2_scene_create derives for a triangle list
+    (rt2_cluster_table_build, host only): one CLUSTER_TABLE_DTYPE record; n = 0
+    when no cluster is compact."""
+    triangles = np.ascontiguousarray(triangles, dtype=TRI_DTYPE)
+    t = np.zeros(1, dtype=CLUSTER_TABLE_DTYPE)
+    if lib().rt2_cluster_table_build(triangles.ctypes.data, len(triangles), t.ctypes.data) < 0:
+        raise RT2Error(f"rt2_cluster_table_build: {lib().rt2_last_error().decode()}")
+    return t[0]
+
+
+def cluster_need(table, o: np.ndarray, d: np.ndarray) -> np.ndarray:
+    """Bit k of element i: ray i (origin o[i], direction d[i]) needs cluster k
+    of `table`, by the arithmetic the kernel runs (rt2_cluster_need, host only)."""
+    t = np.zeros(1, dtype=CLUSTER_TABLE_DTYPE)
+    t[0] = table
+    rays = np.zeros(len(o), dtype=RAY_DTYPE)
+    rays["o"], rays["d"] = o, d
+    bits = np.zeros(len(rays), dtype=np.uint32)
+    _check(lib().rt2_cluster_need(t.ctypes.data, rays.ctypes.data, len(rays), bits.ctypes.data), "rt2_cluster_need")
+    return bits
 
 
 def has_variant(v: int) -> bool:

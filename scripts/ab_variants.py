@@ -82,6 +82,11 @@ for rnd in range(a.rounds):
                 diag[v]["clock_share"] = dict(zip(("advance", "sweep", "shade", "tail"),
                                                   [round(x / sum(tt), 4) for x in tt]))
                 diag[v]["sweep_clocks_per_group"] = round(c[10] / c[2], 1)
+            if c[25] + c[26] + c[27]:  # MfmaSpec::cluster_rows diag (411): (wave, compact cluster) cases of the sweeps
+                cases = c[25] + c[26] + c[27]
+                diag[v]["cluster_rows"] = dict(skipped=round(c[25] / cases, 4), one_block=round(c[26] / cases, 4),
+                                               two_blocks=round(c[27] / cases, 4),
+                                               needing_rays_per_case=round(c[28] / cases, 2))
             tf = [c[13], c[14], c[15], c[16], c[17]]  # render_mfma_k5t tile_flow diag: wait, filter, exact, sweep, life
             if tf[4]:
                 diag[v]["flow_clock_share"] = dict(
