@@ -315,3 +315,108 @@ def test_mutants_fail(oraclemod, scenes, evaluated, mutant):
         ctrl, _ = missed(oraclemod, t, tris, o, d, model_need(t, o, d, margin=False, tris=tris))
         mut, _ = missed(oraclemod, t, tris, o, d, model_need(t, o, d, tris=tris, **kw))
         assert (mut & ~ctrl).any()
+
+
+# ------------------------------------------ comb scenes and the row assignment
+#
+# The premises of tests/test_gpu_cluster_private.py that need no GPU.
+
+@pytest.fixture(scope="module")
+def combs(rt2mod):
+    """Per comb scene: the scene, its explicit table, its primary rays (numpy model of advance())."""
+    out = {}
+    for name in list(cs.COMB_SCENES) + ["full", "ragged"]:
+        sc = cs.named_comb_scene(name)
+        u = cs.comb_uniforms(sc["H"], len(sc["triangles"]))
+        out[name] = (sc, sc["table"](), *cs.camera_rays_model(u))
+    return out
+
+
+def test_comb_need_sets(rt2mod, combs):
+    """Every band's row has the needing set of its interval and every other row
+    none; over the scenes the (c0, c1) the GPU tests stand on are all reached."""
+    reached = set()
+    for name, (sc, t, o, d) in combs.items():
+        cs.check_table(t, sc["triangles"])
+        assert cs.compact_mask(t) == sum(1 << bd["k"] for bd in sc["bands"])
+        bits = rt2mod.cluster_need(t, o, d)
+        assert np.all(bits | cs.compact_mask(t) == (1 << t["n"]) - 1)  # the walls
+        for band, bd in enumerate(sc["bands"]):
+            c0, c1, masks = cs.need_counts(t, o, d, bd["k"])
+            want = sum(1 << x for x in range(bd["x0"], bd["x1"]))
+            for row in range(sc["H"]):
+                assert masks[row] == (want if row == bd["row"] else 0), (name, band, row)
+            reached |= set(zip(c0.tolist(), c1.tolist()))
+    print("(c0, c1) reached:", sorted(reached))
+    missing = [c for c in cs.COMB_REQUIRED if c not in reached]
+    assert not missing, missing
+    assert any(a and b and a + b < 32 for a, b in reached)
+
+
+def test_comb_ownership(oraclemod, combs):
+    """The reference scan gives every owned column its evidence triangle and every other pixel wall triangle 0."""
+    for name, (sc, t, o, d) in combs.items():
+        _, tri, _, _ = oraclemod.closest_hits(sc["triangles"], o, d)
+        want = np.full((sc["H"], cs.COMB_W), sc["wall_tri"], np.int64)
+        for bd in sc["bands"]:
+            assert len(bd["owned"]) == -(-(bd["x1"] - bd["x0"]) // sc["pitch"])
+            want[bd["row"], bd["owned"]] = bd["evidence"]
+            # every group of the cluster holds evidence (where there are as many owned columns as groups)
+            assert len(set((bd["evidence"] >> 5).tolist())) == min(bd["groups"], len(bd["owned"]))
+        assert np.array_equal(tri.reshape(want.shape), want), name
+
+
+def test_comb_controls(rt2mod, combs):
+    """A shrunk box is well-formed and leaves out exactly the victim's ray."""
+    for name, band, (x0, x1), victim in cs.COMB_CONTROLS:
+        sc, t, o, d = combs[name]
+        bd = sc["bands"][band]
+        assert victim in bd["owned"] and bd["x0"] <= x0 < x1 <= bd["x1"]
+        ts = sc["table"]({band: (x0, x1)})
+        k = bd["k"]
+        assert np.all(ts["c"][k]["lo"] < ts["c"][k]["hi"])
+        before, after = cs.need_counts(t, o, d, k)[2], cs.need_counts(ts, o, d, k)[2]
+        assert before[bd["row"]] ^ after[bd["row"]] == 1 << victim
+        other = np.arange(t["n"]) != k
+        assert all(np.array_equal(cs.need_counts(t, o, d, k)[2], cs.need_counts(ts, o, d, k)[2])
+                   for k in np.flatnonzero(other))
+
+
+def check_rows(need):
+    rows0, rows1, src = cs.row_model(need)
+    lanes = [l for l in range(64) if need >> l & 1]
+    c0 = sum(1 for l in lanes if l < 32)
+    assert sorted(rows0) == list(range(32)) and sorted(rows1) == list(range(32))  # each block: a permutation
+    assert src[:len(lanes)] == lanes                                           # rows 0 .. c - 1: the needing lanes
+    assert all(s >= 32 for s in src[c0:])                                      # ... all others from block 1
+    assert not any(s < 32 and not need >> s & 1 for s in src)                  # no filler from block 0
+    assert len(set(src)) == 32
+
+
+def test_row_model():
+    """The row assignment of cluster_rows_frag (rk, rest, the `first` select),
+    restated in cluster_scenes.row_model: for every interval of lanes and 10^4
+    random masks of at most 32 bits, each block's rows are a permutation, the
+    result holds the needing lanes in rows 0 .. c - 1 in lane order, and a lane
+    of block 0 that does not need the cluster is never in the result."""
+    n = 0
+    for a in range(64):
+        for b in range(a, min(a + 32, 64) + 1):
+            check_rows(sum(1 << l for l in range(a, b)))
+            n += 1
+    rng = np.random.default_rng(11)
+    for _ in range(10_000):
+        c = int(rng.integers(0, 33))
+        # all over the wave, or crowded into one block and a little of the other
+        if rng.random() < 0.5:
+            lanes = rng.choice(64, c, replace=False)
+        else:
+            k = int(rng.integers(0, min(c, 4) + 1))
+            blk = int(rng.integers(0, 2))
+            lanes = np.concatenate([32 * blk + rng.choice(32, c - k, replace=False),
+                                    32 * (1 - blk) + rng.choice(32, k, replace=False)])
+        check_rows(sum(1 << int(l) for l in lanes))
+    assert n > 1500
+    # the fillers are block 1's first lanes that do not need the cluster
+    assert cs.row_model(sum(1 << l for l in range(20, 44)))[2][24:] == list(range(44, 52))
+    assert cs.swept_lanes(0) == set() and cs.swept_lanes((1 << 33) - 1) == set(range(64))
