@@ -80,6 +80,15 @@
 // masks can only lose triangles no ray of the wave can hit; the episode builds
 // every ray's pass mask from the unpermuted fragments as before (DESIGN.md
 // "Compact clusters").
+//
+// MfmaSpec::cluster_rows16 (353, 354): a compact cluster that at most 16 live
+// rays need is swept with 16-row products (v_mfma_f32_16x16x32_f16, 4
+// accumulator registers): the rays in one fragment's lower K-half for the
+// group's triangles 0..15 and in another's upper K-half for 16..31, the
+// records read from the same LDS image through the lane's own pointer
+// (cluster_rows_frag16; rt2_mfma.h kt_group16; DESIGN.md "16-row products").
+// Every term is the sum of the same 16 f16 products as in the 32-row form (the
+// other 16 k-slots add zeros), so the filter's guarantee is unchanged.
 #pragma once
 
 // v_writelane_b32 (value and lane wave-uniform).  clang has a builtin for
@@ -379,6 +388,7 @@ __device__ __forceinline__ void phase_prio(int phase) {  // 0 products, 1 exact 
 // three cases and the rays that needed the cluster
 struct ClusterDiag {
     unsigned long long skipped = 0, one = 0, two = 0, rays = 0;
+    unsigned long long r16 = 0;  // ... of `one`, the cases at most 16 rays need (MfmaSpec::cluster_rows16's form)
 };
 
 // MfmaSpec::cluster_rows.  One 32-row fragment out of a0[0] / a0[1] that holds
@@ -414,6 +424,40 @@ __device__ __forceinline__ h8 cluster_rows_frag(const h8* a0, unsigned long long
         r[k] = (uint32_t)(first ? x0 : x1);
     }
     return __builtin_bit_cast(h8, r);
+}
+
+// MfmaSpec::cluster_rows16.  The two 16-row fragments of kt_group16 for the
+// rays of `need` (at most 16 of them): cluster_rows_frag's ranking with other
+// ds_permute destinations.  Row r < 16 of K-half h goes to lane r + 16 h, and
+// row r >= 16 to lane r + 16 + 16 h of 32..63, so every permute is still a
+// permutation of the 64 lanes.  alo is the result with lanes 32..63 zeroed
+// ([rays | 0] over the 32 k-slots), ahi its halves exchanged ([0 | rays]).
+// Rows c .. 15 hold other rays of the wave, as rows c .. 31 do there.
+__device__ __forceinline__ void cluster_rows_frag16(const h8* a0, unsigned long long need, h8& alo, h8& ahi) {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const int l = (int)lane_id();
+    const int c0 = __popc((uint32_t)need), c1 = __popc((uint32_t)(need >> 32));
+    const int rk = (int)lanes_below(need);
+    const bool nb = (need >> l) & 1ull;
+    const int rest = ((l - rk) + (l < 32 ? c0 : c1 + 2 * c0)) & 31;
+    const uint32_t row = (uint32_t)(nb ? rk : rest);
+    const uint32_t dst = row + (row & 16);
+    const auto sw = __builtin_amdgcn_permlane32_swap(dst, dst, false, false);
+    const int half = (l & 32) >> 1;
+    const int to0 = 4 * ((int)sw[0] + half), to1 = 4 * ((int)sw[1] + half);
+    const u4 b0 = __builtin_bit_cast(u4, a0[0]), b1 = __builtin_bit_cast(u4, a0[1]);
+    const bool first = (l & 15) < c0, low = l < 32;
+    u4 rl, rh;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int x0 = __builtin_amdgcn_ds_permute(to0, (int)b0[k]);
+        const int x1 = __builtin_amdgcn_ds_permute(to1, (int)b1[k]);
+        const uint32_t q = (uint32_t)(first ? x0 : x1);
+        rl[k] = low ? q : 0u;
+        rh[k] = __builtin_amdgcn_permlane32_swap(0u, q, false, false)[0];  // [0 | q's lanes 0..31]
+    }
+    alo = __builtin_bit_cast(h8, rl);
+    ahi = __builtin_bit_cast(h8, rh);
 }
 
 template <MfmaSpec S>
@@ -577,6 +621,29 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
                                 tb += kKtOps * 64;
                             }
                         };
+                        // MfmaSpec::cluster_rows16: groups [j, j1) in the 16-row form with fragments
+                        // alo / ahi, two per trip; the lane's own pointer into the same records
+                        // (kt16_record_lane: one ds_read_b128 per quantity, as above)
+                        [[maybe_unused]] auto one_block16 = [&](const h8& alo, const h8& ahi, int j, int j1) {
+                            const int d16 = kt16_record_lane(lane) - lane;
+                            const h8* t = tb + d16;
+                            for (; j + 1 < j1; j += 2) {
+                                uint32_t m0, m1;
+                                kt_group16_2(alo, ahi, t[0], t[64], t[128], t[kKtOps * 64], t[kKtOps * 64 + 64],
+                                             t[kKtOps * 64 + 128], m0, m1);
+                                maskv = rt2_writelane((int)m0, j, maskv);
+                                maskv = rt2_writelane((int)m1, j + 1, maskv);
+                                any |= m0 | m1;
+                                t += 2 * kKtOps * 64;
+                            }
+                            if (j < j1) {
+                                const uint32_t m32 = kt_group16(alo, ahi, t[0], t[64], t[128]);
+                                maskv = rt2_writelane((int)m32, j, maskv);
+                                any |= m32;
+                                t += kKtOps * 64;
+                            }
+                            tb = t - d16;
+                        };
 #pragma nounroll
                         for (int k = 0; k < ncl; k++) {
                             const int g0 = __float_as_int(ct[8 * k + 3]), gf = __float_as_int(ct[8 * k + 7]);
@@ -595,11 +662,22 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
                                         cd->one += 1;
                                     else
                                         cd->two += 1;
+                                    if (c && c <= 16) cd->r16 += 1;
                                 }
                             if (!c) {  // no live ray can meet the box: the groups' hot masks stay 0
                                 tb += (g1 - g0) * (kKtOps * 64);
                                 continue;
                             }
+                            if constexpr (S.cluster_rows16)
+                                if (compact && c <= 16) {
+                                    // whether or not the wave has rays in block 1 (`upper`): the ranking is the
+                                    // same text, and 12 vector instructions fewer per group outweigh the
+                                    // fragment's 40 from a cluster's fourth group on (config B's have 7 and 11)
+                                    h8 alo, ahi;
+                                    cluster_rows_frag16(a0, need, alo, ahi);
+                                    one_block16(alo, ahi, g0, g1);
+                                    continue;
+                                }
                             if (upper && !(compact && c <= 32)) {
                                 // `upper` is true here, but kt_group is to keep the branch on it: folded
                                 // away, a group's products and its fold share a basic block with their
@@ -941,6 +1019,7 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
                 atomicAdd(p.seg_counter + 25, cdg.one);      // ... swept in the one-block form
                 atomicAdd(p.seg_counter + 26, cdg.two);      // ... more than 32 rays need it: two blocks
                 atomicAdd(p.seg_counter + 27, cdg.rays);     // ... the rays that need it, summed
+                atomicAdd(p.seg_counter + 28, cdg.r16);      // ... at most 16 rays need it (and at least one)
             }
         }
 }

@@ -77,6 +77,9 @@ struct MfmaSpec {
                                 // is followed: a compact cluster no live ray needs is skipped, one that at most 32
                                 // need is swept in the one-block form with those rays moved into one fragment
                                 // (rt2_k5_resident.h sweep_kt_res; DESIGN.md "Compact clusters")
+    bool cluster_rows16 = false;  // with cluster_rows: a compact cluster that at most 16 rays need is swept with 16-row
+                                  // products (v_mfma_f32_16x16x32_f16: 4 accumulator registers instead of 16), six per
+                                  // group for the triangles' two halves (kt_group16; DESIGN.md "16-row products")
 };
 
 // per-wave diagnostic counts (wave-uniform; MfmaSpec::diag)
@@ -685,6 +688,77 @@ __device__ __forceinline__ void kt_group_one2(const h8& a, const h8& bu0, const 
     M1 = __ballot(acc1 < 0);
 }
 
+// MfmaSpec::cluster_rows16.  The filter of 16 rays (the form without Y) by
+// v_mfma_f32_16x16x32_f16: A holds row l & 15, B column l & 15, k-slots
+// 8 (l >> 4) .. +7 of 32; D is column l & 15, rows 4 (l >> 4) + reg, in 4
+// registers.  A record register read through kt16_record_lane holds triangle
+// j's 16 slots in the lower K-half of column j and triangle j + 16's in the
+// upper one, so two A fragments give the two halves' exact 16-slot sums from
+// the one B register: alo = [rays | 0] triangles 0..15, ahi = [0 | rays]
+// triangles 16..31 (the other 16 slots add 0 x finite: every f16 of a record is
+// finite, rt2_scene_create asserts it).  Per half 4 ANDs and 2 ORs instead of
+// 16 and 8; a half's ballot has triangle j in bits j, j + 16, j + 32, j + 48.
+__device__ __forceinline__ int kt16_record_lane(int l) { return (l & 15) + 16 * (l >> 5) + 32 * ((l >> 4) & 1); }
+__device__ __forceinline__ int kt16_fold(const f4v& U, const f4v& V, const f4v& X) {
+    int t[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        t[i] = __builtin_amdgcn_bitop3_b32(__float_as_int(U[i]), __float_as_int(V[i]), __float_as_int(X[i]), 0x80);
+    return __builtin_amdgcn_bitop3_b32(t[0], t[1], t[2], 0xFE) | t[3];
+}
+__device__ __forceinline__ uint32_t kt16_hot(unsigned long long Mlo, unsigned long long Mhi) {
+    const uint32_t lo = (uint32_t)(Mlo | Mlo >> 32), hi = (uint32_t)(Mhi | Mhi >> 32);
+    return ((lo | lo >> 16) & 0xffffu) | (hi | hi >> 16) << 16;
+}
+// one group: its hot mask
+__device__ __forceinline__ uint32_t kt_group16(const h8& alo, const h8& ahi, const h8& bu, const h8& bv,
+                                               const h8& bx) {
+    const f4v zero = {};
+    const f4v Ul = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bu, zero, 0, 0, 0);
+    const f4v Vl = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bv, zero, 0, 0, 0);
+    const f4v Xl = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bx, zero, 0, 0, 0);
+    const f4v Uh = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bu, zero, 0, 0, 0);
+    const f4v Vh = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bv, zero, 0, 0, 0);
+    const f4v Xh = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bx, zero, 0, 0, 0);
+    const int al = kt16_fold(Ul, Vl, Xl);
+    const int ah = kt16_fold(Uh, Vh, Xh);
+    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);   // MFMA
+    __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);  // VALU
+    return kt16_hot(__ballot(al < 0), __ballot(ah < 0));
+}
+// two groups per trip, a half's products beside the fold of the half before:
+// [lo0 hi0] [fold lo0] [lo1] [fold hi0] [hi1] [fold lo1] [fold hi1]; at most 36
+// product registers live
+__device__ __forceinline__ void kt_group16_2(const h8& alo, const h8& ahi, const h8& bu0, const h8& bv0,
+                                             const h8& bx0, const h8& bu1, const h8& bv1, const h8& bx1, uint32_t& m0,
+                                             uint32_t& m1) {
+    const f4v zero = {};
+    const f4v Ul0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bu0, zero, 0, 0, 0);
+    const f4v Vl0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bv0, zero, 0, 0, 0);
+    const f4v Xl0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bx0, zero, 0, 0, 0);
+    const f4v Uh0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bu0, zero, 0, 0, 0);
+    const f4v Vh0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bv0, zero, 0, 0, 0);
+    const f4v Xh0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bx0, zero, 0, 0, 0);
+    const int al0 = kt16_fold(Ul0, Vl0, Xl0);
+    const f4v Ul1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bu1, zero, 0, 0, 0);
+    const f4v Vl1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bv1, zero, 0, 0, 0);
+    const f4v Xl1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bx1, zero, 0, 0, 0);
+    const int ah0 = kt16_fold(Uh0, Vh0, Xh0);
+    const f4v Uh1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bu1, zero, 0, 0, 0);
+    const f4v Vh1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bv1, zero, 0, 0, 0);
+    const f4v Xh1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bx1, zero, 0, 0, 0);
+    const int al1 = kt16_fold(Ul1, Vl1, Xl1);
+    const int ah1 = kt16_fold(Uh1, Vh1, Xh1);
+    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);  // MFMA
+    __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);  // VALU
+    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+    __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+    __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);
+    m0 = kt16_hot(__ballot(al0 < 0), __ballot(ah0 < 0));
+    m1 = kt16_hot(__ballot(al1 < 0), __ballot(ah1 < 0));
+}
+
 // Closest hit of every lane's ray (o, d) over all triangles, records read
 // from L2; the whole wave calls it (lanes without a ray of their own carry a
 // copy of a live one).  Five products per 32-ray block: U, -V, X from the
@@ -1016,7 +1090,8 @@ __device__ __forceinline__ K16Terms k16_terms(const h8& a0, const h8& a1, const 
 // LAYOUT: rt2_mfma_probe's (rt2_render.hip) — 0 = the 16x16x32 form, 1 = the
 // 8-product k16 form, 2 = the 5-product form, 3 = the 5-product form with the
 // threshold in the accumulator, 4 = layout 3 on frag_pair fragments, 5 = the
-// threshold in the K-slots, 6 = layout 5 with each ray's own W.
+// threshold in the K-slots, 6 = layout 5 with each ray's own W, 7 = layout 6's
+// U, -V, X by the 16-row products (MfmaSpec::cluster_rows16).
 template <int LAYOUT>
 __global__ __launch_bounds__(64) void mfma_probe_kernel(RenderParams p, const float4* rays, int n_pad, float* terms,
                                                         _Float16* frags, float* rinfo, uint8_t* accept) {
@@ -1070,7 +1145,7 @@ __global__ __launch_bounds__(64) void mfma_probe_kernel(RenderParams p, const fl
         [[maybe_unused]] ThrBits tb = {};
         [[maybe_unused]] _Float16 tw16 = (_Float16)0.0f;
         if constexpr (kKthr) {
-            kt_frags<LAYOUT == 6>(d, m, sc, a0, tw16);
+            kt_frags<LAYOUT >= 6>(d, m, sc, a0, tw16);
             kt_y(d, o, bestK, sc, tw16, y1);
         } else {
             _Float16 s[18];
@@ -1092,6 +1167,42 @@ __global__ __launch_bounds__(64) void mfma_probe_kernel(RenderParams p, const fl
         const h8* fg = reinterpret_cast<const h8*>(kKthr ? p.mfma_kt_frag : p.mfma_k16_frag) + lane;
         const int nops = kKthr ? kKtOps : kK16Ops;
         const f16v zero = {};
+        if constexpr (LAYOUT == 7) {
+            // MfmaSpec::cluster_rows16: U, -V, X of layout 6 by kt_group16's
+            // products.  Each 16 rays of the wave in turn are the 16 rows:
+            // alo = [rows | 0], ahi = [0 | rows]; the records through
+            // kt16_record_lane.  T and Y stay 0 (the form has no Y).
+            typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+            const h8* fg16 = reinterpret_cast<const h8*>(p.mfma_kt_frag) + kt16_record_lane(lane);
+            const f4v zero4 = {};
+            for (int R16 = 0; R16 < 4; R16++) {
+                const u4 src = __builtin_bit_cast(u4, a0[R16 >> 1]);
+                u4 lo, hi;
+                for (int k = 0; k < 4; k++) {
+                    const uint32_t v = (uint32_t)__shfl((int)src[k], 16 * (R16 & 1) + (lane & 15) + 32 * ((lane >> 4) & 1));
+                    lo[k] = lane < 32 ? v : 0u;
+                    hi[k] = lane < 32 ? 0u : v;
+                }
+                const h8 alo = __builtin_bit_cast(h8, lo), ahi = __builtin_bit_cast(h8, hi);
+                for (int G = 0; G < n_pad / 32; G++) {
+                    const h8* t = fg16 + (size_t)G * kKtOps * 64;
+                    f4v q[2][3];
+                    for (int op = 0; op < 3; op++) {
+                        q[0][op] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, t[64 * op], zero4, 0, 0, 0);
+                        q[1][op] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, t[64 * op], zero4, 0, 0, 0);
+                    }
+                    for (int h = 0; h < 2; h++)
+                        for (int i = 0; i < 4; i++) {
+                            const size_t rr = ray0 + 16 * R16 + 4 * (lane >> 4) + i;
+                            float* tt = terms + (rr * n_pad + 32 * G + 16 * h + (lane & 15)) * 5;
+                            tt[0] = q[h][0][i];
+                            tt[1] = q[h][1][i];
+                            tt[2] = q[h][2][i];
+                        }
+                }
+            }
+            return;
+        }
         for (int G = 0; G < n_pad / 32; G++) {
             h8 b[kK16Ops];
             for (int op = 0; op < nops; op++) b[op] = fg[(size_t)G * nops * 64 + 64 * op];

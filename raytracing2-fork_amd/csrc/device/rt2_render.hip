@@ -468,6 +468,16 @@ static int scene_init(rt2_scene* s, const rt2_triangle* tris, int32_t n_tris, co
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipDeviceSynchronize());
         HIPCHECK(hipMemset(d_mflags, 0, 2 * sizeof(uint32_t)));
+        // MfmaSpec::cluster_rows16 multiplies every record slot of a resident scene by a zero of the other
+        // triangle half's fragment: every f16 must be finite, the padding columns' too (0 x inf is NaN).
+        // mfma_slots makes them from coefficients the range check bounds; this checks the bits once per scene.
+        // A scene that fails leaves the matrix filter's range like one with a coordinate above 2^20.
+        if (s->mfma_ok && n_pad32 / 32 <= kResGroups) {
+            std::vector<uint16_t> rec(kt_bytes / sizeof(uint16_t));
+            HIPCHECK(hipMemcpy(rec.data(), s->d_mfma_kt, kt_bytes, hipMemcpyDeviceToHost));
+            for (uint16_t h : rec)
+                if ((h & 0x7c00u) == 0x7c00u) s->mfma_ok = 0;
+        }
     }
     HIPCHECK(hipDeviceSynchronize());
     return 0;
@@ -634,6 +644,13 @@ constexpr MfmaSpec kt_cr(MfmaSpec x) {
     x.cluster_rows = true;
     return x;
 }
+// ... and a compact cluster that at most 16 rays need with 16-row products (MfmaSpec::cluster_rows16; DESIGN.md
+// "16-row products")
+constexpr MfmaSpec kt_cr16(MfmaSpec x) {
+    x.cluster_rows = true;
+    x.cluster_rows16 = true;
+    return x;
+}
 constexpr int kResWin = 38;  // the window of 353-356 (and the diagnostic 350): the whole resident sweep, then one episode
 constexpr int kResL2Groups = 256;  // render_mfma_k5r with res_l2: kResGroups groups resident, the rest from L2
 // records streamed through LDS tiles (rt2_k5_tiles.h): 19-group tiles, each ray's own W, issue priority by
@@ -680,8 +697,8 @@ constexpr Variant kVariants[] = {
     // (DESIGN.md "Exact tests per ray"), two groups per trip of the products' loop with the hot masks by v_writelane
     // (DESIGN.md "Two groups per loop trip") and keep each pixel's camera end point in LDS instead of recomputing it
     // per ray (DESIGN.md "The camera end point once per pixel")
-    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_cr(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
-    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_cr(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
+    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
+    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
     RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, true, 4), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
     RT2_VARIANT(356, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, true, true), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw", kResL2Groups),
     // the default above 8,192 triangles: the LDS-tiled kernel (rt2_k5_tiles.h; 19-group tiles, fragments in
@@ -736,7 +753,11 @@ constexpr Variant kVariants[] = {
     // the form before), and the diagnostic build that counts the skipped / one-block / two-block cases
     RT2_VARIANT(409, K_MFMA, render_mfma_k5r<kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/nocr", kResGroups),
     RT2_VARIANT(410, K_MFMA, render_mfma_k5r<kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/nocr", kResGroups),
-    RT2_VARIANT(411, K_MFMA, render_mfma_k5r<kt_cr(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 0, true), kResWin))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/xl/cr", kResGroups),
+    RT2_VARIANT(411, K_MFMA, render_mfma_k5r<kt_cr16(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 0, true), kResWin))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/xl/cr16", kResGroups),
+    // the 16-row products for clusters that at most 16 rays need (MfmaSpec::cluster_rows16; 353 / 354 and the
+    // diagnostic 411 take it): 353's and 354's specs with the cluster table alone (cr32: the form before)
+    RT2_VARIANT(412, K_MFMA, render_mfma_k5r<kt_cr(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/cr32", kResGroups),
+    RT2_VARIANT(413, K_MFMA, render_mfma_k5r<kt_cr(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/cr32", kResGroups),
     // the tile stream at 3 waves per SIMD (380 takes 4 with the lean lane state): with its diagnostic clocks; without
     // flow_prio; with the lean lane state
     RT2_VARIANT(370, K_MFMA, render_mfma_k5t<kt_tiles_flow()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp"),
@@ -1904,7 +1925,8 @@ extern "C" int rt2_scene_set_clusters(rt2_scene* s, const rt2_cluster_table* t) 
 // -tn slot), 4 = layout 3 with the fragments built in registers by frag_pair,
 // 5 = the threshold in the K-slots (render_mfma_k5r / render_mfma_k5t,
 // frag_pair fragments: U, -V, X, Y, slot 3 zero), 6 = layout 5 with each
-// ray's own W (MfmaSpec::kt_lane_w).
+// ray's own W (MfmaSpec::kt_lane_w), 7 = layout 6's U, -V, X by the 16-row
+// products of MfmaSpec::cluster_rows16 (kt_group16's operands; terms 3, 4 stay 0).
 // Host outputs, sized by the caller: terms [n_rays][n_pad][5]
 // (n_pad = triangles padded to 16 / 32), frags [n_rays][80] f16 bits (the LDS
 // row of layouts 0..3: main slots 0..31 and Y slots 16..31; layouts 4, 5 also
@@ -1913,7 +1935,7 @@ extern "C" int rt2_scene_set_clusters(rt2_scene* s, const rt2_cluster_table* t) 
 extern "C" int rt2_mfma_probe(rt2_scene* s, int layout, const float* rays, int32_t n_rays, float* terms,
                               uint16_t* frags, float* rinfo, uint8_t* accept) {
     if (!s || !rays || n_rays <= 0 || n_rays % 64 != 0 || !terms || !frags || !rinfo || !accept ||
-        layout < 0 || layout > 6 || s->n_tris < 1 || !s->mfma_ok) {
+        layout < 0 || layout > 7 || s->n_tris < 1 || !s->mfma_ok) {
         rt2h::set_error("rt2_mfma_probe: bad argument (n_rays a positive multiple of 64, a scene in the filter's "
                         "range)");
         return -1;
@@ -1958,7 +1980,8 @@ extern "C" int rt2_mfma_probe(rt2_scene* s, int layout, const float* rays, int32
         case 3: launch(mfma_probe_kernel<3>); break;
         case 4: launch(mfma_probe_kernel<4>); break;
         case 5: launch(mfma_probe_kernel<5>); break;
-        default: launch(mfma_probe_kernel<6>); break;
+        case 6: launch(mfma_probe_kernel<6>); break;
+        default: launch(mfma_probe_kernel<7>); break;
         }
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipDeviceSynchronize());

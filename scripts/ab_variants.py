@@ -86,7 +86,12 @@ for rnd in range(a.rounds):
                 cases = c[25] + c[26] + c[27]
                 diag[v]["cluster_rows"] = dict(skipped=round(c[25] / cases, 4), one_block=round(c[26] / cases, 4),
                                                two_blocks=round(c[27] / cases, 4),
-                                               needing_rays_per_case=round(c[28] / cases, 2))
+                                               needing_rays_per_case=round(c[28] / cases, 2),
+                                               # ... of one_block, at most 16 rays need it (MfmaSpec::cluster_rows16)
+                                               rows16=round(c[29] / cases, 4),
+                                               counts=dict(skipped=int(c[25]), one_block=int(c[26]),
+                                                           two_blocks=int(c[27]), needing_rays=int(c[28]),
+                                                           rows16=int(c[29])))
             tf = [c[13], c[14], c[15], c[16], c[17]]  # render_mfma_k5t tile_flow diag: wait, filter, exact, sweep, life
             if tf[4]:
                 diag[v]["flow_clock_share"] = dict(
