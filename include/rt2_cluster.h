@@ -84,6 +84,14 @@ struct rt2_ray;
  * scene of at most 38 groups).  Returns the number of clusters, < 0 on a bad
  * argument.  Host only: no device is touched. */
 int rt2_cluster_table_build(const struct rt2_triangle* tris, int32_t n_tris, rt2_cluster_table* out);
+/* The slot order of a scene of at most 38 groups (DESIGN.md "Slot order"):
+ * slot_tri is a permutation of [0, n_tris), slot s holds triangle slot_tri[s],
+ * group g the slots 32 g .. 32 g + 31, and `out` is the table over those slot
+ * groups.  The rule reads the vertices only and is deterministic.  Where its
+ * own order does not project cheaper than the index order, the result is the
+ * identity and rt2_cluster_table_build's table.  Returns the number of
+ * clusters, < 0 on a bad argument.  Host only. */
+int rt2_cluster_order_build(const struct rt2_triangle* tris, int32_t n_tris, int32_t* slot_tri, rt2_cluster_table* out);
 /* bits[i]: bit k set when ray i needs cluster k (a full cluster's bit is always
  * set; a ray outside the filter's range, which the kernel hands to its drain,
  * gets every bit).  Host only. */

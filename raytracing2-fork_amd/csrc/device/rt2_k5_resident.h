@@ -89,6 +89,14 @@
 // (cluster_rows_frag16; rt2_mfma.h kt_group16; DESIGN.md "16-row products").
 // Every term is the sum of the same 16 f16 products as in the 32-row form (the
 // other 16 k-slots add zeros), so the filter's guarantee is unchanged.
+//
+// MfmaSpec::slot_order (353, 354): the scene's triangles are regrouped by
+// place at upload (rt2_cluster_order_build) and the sweep reads that slot
+// image: records, table and the episode's triangles in slot order.  A ray's
+// survivors are then tested in ascending slot, not index; mt_exact_slot takes
+// the lower index on equal distances, which leaves the index-order scan's
+// result, and the hit's slot is mapped to its index after the sweep (DESIGN.md
+// "Slot order").
 #pragma once
 
 // v_writelane_b32 (value and lane wave-uniform).  clang has a builtin for
@@ -174,8 +182,10 @@ __host__ __device__ constexpr int xl_bit_of_row(int r) { return 16 * ((r >> 2) &
 //     loads, then the unchanged mt_quantities / mt_pass3 / mt_exact.
 // Rounds ascend and a lane's bits ascend, so every ray sees its surviving
 // pairs in index order against its current bound: the sequential strict `dst <
-// best` scan.  The filter's guarantee is per (ray, triangle) pair (DESIGN.md
-// "Exact tests per ray"), so a ray may skip what other rays of its wave test.
+// best` scan.  MfmaSpec::slot_order: maskv, recs, tri4 and the list are in
+// slot order, and mt_exact_slot's tie rule keeps the scan's result.  The
+// filter's guarantee is per (ray, triangle) pair (DESIGN.md "Exact tests per
+// ray"), so a ray may skip what other rays of its wave test.
 // upper = false: lanes 32..63 hold no ray of their own and get a zero mask.
 // LDS: the records of every group of the window are resident (recs = the
 // LDS copy); else recs = the scene's kt records in global memory.
@@ -183,7 +193,7 @@ template <MfmaSpec S, bool YP, bool LDS, class Rebuild>
 __device__ __forceinline__ void exact_window_lanes(int maskv, int Gw, bool more, int n_tris, const float4* tri4,
                                                    const h8* a0, const h8* y1, const h8* recs, bool upper, const f3& o,
                                                    const f3& d, float& best, int& bi, float& bestK, MfmaDiag& dg,
-                                                   Rebuild rebuild) {
+                                                   Rebuild rebuild, [[maybe_unused]] const int* slot_tri = nullptr) {
     const int lane = (int)lane_id();
     [[maybe_unused]] unsigned long long tc = 0;
     if constexpr (S.diag) {
@@ -284,7 +294,12 @@ __device__ __forceinline__ void exact_window_lanes(int maskv, int Gw, bool more,
             fetch(nxt);
             if (has) {
                 const MtQ qq = mt_quantities(o, d, cur.t0, cur.t1, cur.t2);
-                if (mt_pass3(qq, bestK)) mt_exact(qq, cur.idx, best, bi, bestK);
+                if (mt_pass3(qq, bestK)) {
+                    if constexpr (S.slot_order)
+                        mt_exact_slot(qq, cur.idx, slot_tri, best, bi, bestK);
+                    else
+                        mt_exact(qq, cur.idx, best, bi, bestK);
+                }
             }
         };
         Tri ta, tb2;
@@ -460,6 +475,21 @@ __device__ __forceinline__ void cluster_rows_frag16(const h8* a0, unsigned long 
     ahi = __builtin_bit_cast(h8, rh);
 }
 
+// MfmaSpec::slot_order.  The slot image of a resident scene, one allocation
+// that RenderParams::mfma_kt_frag points at: the kt records of the triangles
+// in slot order, the table over the slot groups (where the index image has its
+// own), the prepared triangles in slot order (3 float4 each) and slot_tri.
+struct SlotImage {
+    const float4* tri4;
+    const int* slot_tri;
+};
+__device__ __forceinline__ SlotImage slot_image(const RenderParams& p) {
+    const int ng = (p.n_tris + 31) >> 5;
+    const char* tab = reinterpret_cast<const char*>(reinterpret_cast<const h8*>(p.mfma_kt_frag) + (size_t)ng * (kKtOps * 64));
+    const float4* t4 = reinterpret_cast<const float4*>(tab + sizeof(rt2_cluster_table));
+    return {t4, reinterpret_cast<const int*>(t4 + 3 * (size_t)p.n_tris)};
+}
+
 template <MfmaSpec S>
 __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* rec, const f3& o, const f3& d,
                                              float& best, int& bi, float& bestK, MfmaDiag& dg, bool upper,
@@ -491,6 +521,11 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
     const int nres = S.res_l2 ? min(ng, kResGroups) : ng;
     cfloat* const tri = (cfloat*)p.tri;  // held across the sweep (not re-read from the kernel arguments per hot group)
     const h8* tb = rec + lane;
+    [[maybe_unused]] const int* slot_tri = nullptr;
+    if constexpr (S.slot_order) {
+        static_assert(S.cluster_rows && S.exact_lanes && !S.res_l2, "slot_order: 353 / 354's one resident window");
+        slot_tri = slot_image(p).slot_tri;
+    }
     if constexpr (per_group) {
         // one exact episode per hot group, the bound rebuilt after each
         for (int G = 0; G < nres; G++) {
@@ -716,11 +751,12 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
                 if constexpr (S.exact_lanes) {
                     static_assert(W > 1, "exact_lanes reads the window's masks from maskv");
                     const float4* tri4 = reinterpret_cast<const float4*>(p.tri);
+                    if constexpr (S.slot_order) tri4 = slot_image(p).tri4;
                     auto rebuild = [&] { kt_y(d, o, bestK, sc, tw16, y1); };
                     // a first window is resident; the L2 loop's windows gather from the scene's records
                     if (!YP || resident)
                         exact_window_lanes<S, YP, true>(maskv, Gw, more, n_tris, tri4, a0, y1, rec, upper, o, d, best,
-                                                        bi, bestK, dg, rebuild);
+                                                        bi, bestK, dg, rebuild, slot_tri);
                     else if constexpr (YP)
                         exact_window_lanes<S, YP, false>(maskv, Gw, more, n_tris, tri4, a0, y1,
                                                          reinterpret_cast<const h8*>(p.mfma_kt_frag), upper, o, d, best,
@@ -759,6 +795,9 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
             windows(std::true_type{}, reinterpret_cast<const h8*>(p.mfma_kt_frag) + (size_t)nres * (kKtOps * 64) + lane,
                     nres, ng, false);
     }
+    // MfmaSpec::slot_order: the hit's slot becomes its triangle's index, once per sweep
+    if constexpr (S.slot_order)
+        if (bi >= 0) bi = slot_tri[bi];
     if constexpr (S.diag) dg.t_swp += __builtin_amdgcn_s_memtime() - tsw;
     return true;
 }

@@ -80,6 +80,10 @@ struct MfmaSpec {
     bool cluster_rows16 = false;  // with cluster_rows: a compact cluster that at most 16 rays need is swept with 16-row
                                   // products (v_mfma_f32_16x16x32_f16: 4 accumulator registers instead of 16), six per
                                   // group for the triangles' two halves (kt_group16; DESIGN.md "16-row products")
+    bool slot_order = false;  // with cluster_rows and exact_lanes: RenderParams::mfma_kt_frag is the scene's slot image
+                              // (records, table, triangles and slot_tri of the triangles in slot order); the episode
+                              // breaks distance ties by the triangles' indices and the sweep returns an index
+                              // (rt2_k5_resident.h slot_image; DESIGN.md "Slot order")
 };
 
 // per-wave diagnostic counts (wave-uniform; MfmaSpec::diag)

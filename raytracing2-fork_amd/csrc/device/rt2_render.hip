@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -87,6 +88,10 @@ struct rt2_scene {
     _Float16* d_mfma_kt = nullptr;              // kthr records (threshold in the K-slots: 4 KiB per 32 triangles)
     int mfma_ok = 0;                            // render_mfma usable (records built, scene in range)
     rt2_cluster_table clusters = {};            // MfmaSpec::cluster_rows: the groups' clusters (n = 0: none compact)
+    void* d_slot = nullptr;                     // MfmaSpec::slot_order: the slot image of a scene of <= kResGroups groups
+                                                // (kt records, slot table, prepared triangles, slot_tri, in slot order)
+    rt2_cluster_table slot_table = {};          // ... its table over the slot groups
+    std::vector<int32_t> slot_tri;              // ... slot s holds triangle slot_tri[s]
     float mfma_A = 0.0f;                        // max |a_i| over the in-range triangles
     float4* d_fb = nullptr;                     // frame_split scratch (per-frame colours)
     uchar4* d_texels = nullptr;                 // textures, RGBA8
@@ -338,6 +343,7 @@ extern "C" int rt2_scene_set_traversal(rt2_scene* s, int traversal) {
 
 static int scene_init(rt2_scene* s, const rt2_triangle* tris, int32_t n_tris, const rt2_material* mats,
                       int32_t n_mats, const rt2_node* nodes, int32_t n_nodes, int32_t device);
+static int build_slot_image(rt2_scene* s);
 
 extern "C" int rt2_scene_create(const rt2_triangle* tris, int32_t n_tris, const rt2_material* mats, int32_t n_mats,
                                 const rt2_node* nodes, int32_t n_nodes, int32_t device, rt2_scene** out) {
@@ -477,9 +483,47 @@ static int scene_init(rt2_scene* s, const rt2_triangle* tris, int32_t n_tris, co
             HIPCHECK(hipMemcpy(rec.data(), s->d_mfma_kt, kt_bytes, hipMemcpyDeviceToHost));
             for (uint16_t h : rec)
                 if ((h & 0x7c00u) == 0x7c00u) s->mfma_ok = 0;
+            // the slot order of 353 / 354 (MfmaSpec::slot_order; DESIGN.md "Slot order") and its image
+            s->slot_tri.resize((size_t)n_tris);
+            if (rt2_cluster_order_build(tris, n_tris, s->slot_tri.data(), &s->slot_table) < 0) return -1;
+            if (build_slot_image(s) != 0) return -1;
         }
     }
     HIPCHECK(hipDeviceSynchronize());
+    return 0;
+}
+
+// The slot image of a resident scene (rt2_k5_resident.h slot_image): the kt records of the triangles in the order
+// s->slot_tri, s->slot_table, the prepared triangles in that order and slot_tri itself, in one allocation.  The
+// finite-f16 check of the index image's records covers these too.
+static int build_slot_image(rt2_scene* s) {
+    const int n = s->n_tris, n_pad32 = (n + 31) / 32 * 32;
+    if (n <= 0 || n_pad32 / 32 > kResGroups || !s->d_mfma_kt || (int)s->slot_tri.size() != n) return 0;
+    const size_t kt_bytes = (size_t)n_pad32 * kKtOps * 16 * sizeof(_Float16), tab = sizeof(rt2_cluster_table);
+    const size_t tri_bytes = (size_t)n * 3 * sizeof(float4);
+    const size_t total = kt_bytes + tab + tri_bytes + (size_t)n * sizeof(int32_t);
+    if (!s->d_slot) HIPCHECK(hipMalloc(&s->d_slot, total));
+    char* base = reinterpret_cast<char*>(s->d_slot);
+    std::vector<float4> tri((size_t)n * 3), perm((size_t)n * 3);
+    HIPCHECK(hipMemcpy(tri.data(), s->d_tri, tri_bytes, hipMemcpyDeviceToHost));
+    for (int k = 0; k < n; k++) std::copy_n(&tri[3 * (size_t)s->slot_tri[k]], 3, &perm[3 * (size_t)k]);
+    HIPCHECK(hipMemcpy(base + kt_bytes, &s->slot_table, tab, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(base + kt_bytes + tab, perm.data(), tri_bytes, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(base + kt_bytes + tab + tri_bytes, s->slot_tri.data(), (size_t)n * sizeof(int32_t),
+                       hipMemcpyHostToDevice));
+    uint32_t* d_mflags = reinterpret_cast<uint32_t*>(s->d_counters + kCounters - 2);
+    hipLaunchKernelGGL(prep_mfma_kt, dim3((n_pad32 + 255) / 256), dim3(256), 0, 0,
+                       reinterpret_cast<const float4*>(base + kt_bytes + tab), n, n_pad32,
+                       reinterpret_cast<_Float16*>(base), d_mflags);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemset(d_mflags, 0, 2 * sizeof(uint32_t)));
+    if (s->mfma_ok) {
+        std::vector<uint16_t> rec(kt_bytes / sizeof(uint16_t));
+        HIPCHECK(hipMemcpy(rec.data(), base, kt_bytes, hipMemcpyDeviceToHost));
+        for (uint16_t h : rec)
+            if ((h & 0x7c00u) == 0x7c00u) s->mfma_ok = 0;
+    }
     return 0;
 }
 
@@ -520,6 +564,7 @@ extern "C" void rt2_scene_destroy(rt2_scene* s) {
     (void)hipFree(s->d_mfma_k16_tau);
     (void)hipFree(s->d_mfma_k16_bnd);
     (void)hipFree(s->d_mfma_kt);
+    (void)hipFree(s->d_slot);
     (void)hipFree(s->d_fb);
     (void)hipFree(s->d_cost);
     (void)hipFree(s->d_order);
@@ -576,6 +621,7 @@ struct Variant {
     void (*kernel)(RenderParams);
     const char* name;
     int max_groups = 0;  // largest scene the kernel holds, in 32-triangle groups (0 = no limit)
+    bool slot = false;   // MfmaSpec::slot_order: RenderParams::mfma_kt_frag is the scene's slot image
 };
 
 template <auto K, int BLOCK>
@@ -651,6 +697,12 @@ constexpr MfmaSpec kt_cr16(MfmaSpec x) {
     x.cluster_rows16 = true;
     return x;
 }
+// ... on the scene's slot image: triangles regrouped by place, groups swept in slot order (MfmaSpec::slot_order;
+// DESIGN.md "Slot order")
+constexpr MfmaSpec kt_slot(MfmaSpec x) {
+    x.slot_order = true;
+    return x;
+}
 constexpr int kResWin = 38;  // the window of 353-356 (and the diagnostic 350): the whole resident sweep, then one episode
 constexpr int kResL2Groups = 256;  // render_mfma_k5r with res_l2: kResGroups groups resident, the rest from L2
 // records streamed through LDS tiles (rt2_k5_tiles.h): 19-group tiles, each ray's own W, issue priority by
@@ -697,8 +749,9 @@ constexpr Variant kVariants[] = {
     // (DESIGN.md "Exact tests per ray"), two groups per trip of the products' loop with the hot masks by v_writelane
     // (DESIGN.md "Two groups per loop trip") and keep each pixel's camera end point in LDS instead of recomputing it
     // per ray (DESIGN.md "The camera end point once per pixel")
-    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups),
-    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups),
+    // and sweep the scene's slot image (DESIGN.md "Slot order")
+    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_slot(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups, true),
+    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_slot(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups, true),
     RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, true, 4), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
     RT2_VARIANT(356, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, true, true), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw", kResL2Groups),
     // the default above 8,192 triangles: the LDS-tiled kernel (rt2_k5_tiles.h; 19-group tiles, fragments in
@@ -758,6 +811,11 @@ constexpr Variant kVariants[] = {
     // diagnostic 411 take it): 353's and 354's specs with the cluster table alone (cr32: the form before)
     RT2_VARIANT(412, K_MFMA, render_mfma_k5r<kt_cr(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/cr32", kResGroups),
     RT2_VARIANT(413, K_MFMA, render_mfma_k5r<kt_cr(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/cr32", kResGroups),
+    // the slot image (MfmaSpec::slot_order; 353 / 354 take it): 353's and 354's specs on the index image (idx: the form
+    // before), and 411's counters on the slot image
+    RT2_VARIANT(414, K_MFMA, render_mfma_k5r<kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/idx", kResGroups),
+    RT2_VARIANT(415, K_MFMA, render_mfma_k5r<kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/idx", kResGroups),
+    RT2_VARIANT(416, K_MFMA, render_mfma_k5r<kt_slot(kt_cr16(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 0, true), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/xl/cr16/slot", kResGroups, true),
     // the tile stream at 3 waves per SIMD (380 takes 4 with the lean lane state): with its diagnostic clocks; without
     // flow_prio; with the lean lane state
     RT2_VARIANT(370, K_MFMA, render_mfma_k5t<kt_tiles_flow()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp"),
@@ -1145,6 +1203,13 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
         blocks = std::min(blocks, (p.n_items + rays_per_block - 1) / rays_per_block);
     }
     blocks = std::max(blocks, 1ull);
+    if (V.slot) {
+        if (!s->d_slot) {
+            rt2h::set_error("rt2_render: the scene has no slot image");
+            return -1;
+        }
+        p.mfma_kt_frag = reinterpret_cast<const _Float16*>(s->d_slot);
+    }
     s->last_variant = V.id;
     HIPCHECK(V.launch(p, (int)blocks, lds, st));
     HIPCHECK(hipGetLastError());
@@ -1854,8 +1919,9 @@ extern "C" int rt2_device_selftest(const float* in, int32_t n, float* out10) {
 // records in the 16x16x32 layout, 2 = their per-triangle tau, 3 = sweep_k16 records,
 // 4 = their tau, 5 = the k5 form's per-triangle m.z residual bounds, 6 = the
 // kthr records (threshold in the K-slots), 7 = the cluster table (rt2_cluster_table of rt2_cluster.h, the host's
-// copy; n = 0 when the scene has no compact cluster).  Returns the array's size in bytes (nothing copied when
-// `host` is null or `bytes` is too small), < 0 on error.
+// copy; n = 0 when the scene has no compact cluster), 8 = the table over the slot groups of the resident kernel's slot
+// image, 9 = its slot_tri (int32 per triangle; empty for a scene without the image).  Returns the array's size in
+// bytes (nothing copied when `host` is null or `bytes` is too small), < 0 on error.
 extern "C" long long rt2_scene_export(rt2_scene* s, int what, void* host, unsigned long long bytes) {
     if (!s) return -1;
     const size_t n = (size_t)std::max(s->n_tris, 1), n16 = (size_t)(s->n_tris + 15) / 16 * 16,
@@ -1866,6 +1932,15 @@ extern "C" long long rt2_scene_export(rt2_scene* s, int what, void* host, unsign
     if (what == 7) {
         if (host && bytes >= sizeof(s->clusters)) std::memcpy(host, &s->clusters, sizeof(s->clusters));
         return (long long)sizeof(s->clusters);
+    }
+    if (what == 8) {
+        if (host && bytes >= sizeof(s->slot_table)) std::memcpy(host, &s->slot_table, sizeof(s->slot_table));
+        return (long long)sizeof(s->slot_table);
+    }
+    if (what == 9) {
+        const size_t b = s->slot_tri.size() * sizeof(int32_t);
+        if (host && b && bytes >= b) std::memcpy(host, s->slot_tri.data(), b);
+        return (long long)b;
     }
     switch (what) {
     case 0: src = s->d_tri, sz = n * 3 * sizeof(float4); break;
@@ -1886,16 +1961,8 @@ extern "C" long long rt2_scene_export(rt2_scene* s, int what, void* host, unsign
     return (long long)sz;
 }
 
-// Not in rt2.h (test hook): replaces the scene's cluster table (rt2_cluster.h) by the caller's, for tests that
-// need clusters the upload rule would not choose.  The ranges must be contiguous and cover the scene's groups (the
-// kernel steps through the resident records by them); that every triangle lies inside its cluster's box is the
-// caller's business: a box that leaves one out loses hits, nothing else.  n = 0 switches the clusters off.
-extern "C" int rt2_scene_set_clusters(rt2_scene* s, const rt2_cluster_table* t) {
-    if (!s || !t || !s->d_mfma_kt) {
-        rt2h::set_error("rt2_scene_set_clusters: bad argument (a scene with matrix-filter records)");
-        return -1;
-    }
-    const int ng = (s->n_tris + 31) / 32;
+// A caller's table: contiguous ranges that cover the scene's ng groups (n = 0: no clusters)
+static bool cluster_table_covers(const rt2_cluster_table* t, int ng) {
     bool ok = t->n >= 0 && t->n <= RT2_MAX_CLUSTERS && (t->n == 0 || ng <= kResGroups) && t->far_o >= 0.0f;
     int g = 0;
     for (int k = 0; ok && k < t->n; k++) {
@@ -1903,7 +1970,22 @@ extern "C" int rt2_scene_set_clusters(rt2_scene* s, const rt2_cluster_table* t) 
         ok = t->c[k].g0 == g && g1 > g && (t->c[k].g1_flags & ~(0xffff | RT2_CLUSTER_COMPACT)) == 0;
         g = g1;
     }
-    if (!ok || (t->n > 0 && g != ng)) {
+    return ok && (t->n == 0 || g == ng);
+}
+
+// Not in rt2.h (test hook): replaces the scene's cluster table (rt2_cluster.h) by the caller's, for tests that
+// need clusters the upload rule would not choose.  The ranges must be contiguous and cover the scene's groups (the
+// kernel steps through the resident records by them); that every triangle lies inside its cluster's box is the
+// caller's business: a box that leaves one out loses hits, nothing else.  n = 0 switches the clusters off.
+// This index-order table also becomes the slot image's, with the identity order: 353 / 354 then sweep what the
+// kernels on the index image sweep.
+extern "C" int rt2_scene_set_clusters(rt2_scene* s, const rt2_cluster_table* t) {
+    if (!s || !t || !s->d_mfma_kt) {
+        rt2h::set_error("rt2_scene_set_clusters: bad argument (a scene with matrix-filter records)");
+        return -1;
+    }
+    const int ng = (s->n_tris + 31) / 32;
+    if (!cluster_table_covers(t, ng)) {
         rt2h::set_error("rt2_scene_set_clusters: the ranges must be contiguous and cover the scene's groups");
         return -1;
     }
@@ -1913,7 +1995,40 @@ extern "C" int rt2_scene_set_clusters(rt2_scene* s, const rt2_cluster_table* t) 
     const size_t kt_bytes = (size_t)ng * 32 * kKtOps * 16 * sizeof(_Float16);
     HIPCHECK(hipMemcpy(reinterpret_cast<char*>(s->d_mfma_kt) + kt_bytes, &s->clusters, sizeof(s->clusters),
                        hipMemcpyHostToDevice));
+    if (s->d_slot) {
+        std::iota(s->slot_tri.begin(), s->slot_tri.end(), 0);
+        s->slot_table = *t;
+        if (build_slot_image(s) != 0) return -1;
+    }
     return 0;
+}
+
+// Not in rt2.h (test hook): installs an explicit slot order (a permutation of the scene's triangle indices) and
+// its table over the slot groups, for a scene of at most kResGroups groups.  The table's rules are
+// rt2_scene_set_clusters'; the index image and its table are not touched.
+extern "C" int rt2_scene_set_slot_order(rt2_scene* s, const int32_t* slot_tri, const rt2_cluster_table* t) {
+    if (!s || !slot_tri || !t || !s->d_slot) {
+        rt2h::set_error("rt2_scene_set_slot_order: bad argument (a scene with a slot image)");
+        return -1;
+    }
+    const int ng = (s->n_tris + 31) / 32;
+    std::vector<char> seen((size_t)s->n_tris, 0);
+    for (int k = 0; k < s->n_tris; k++) {
+        if (slot_tri[k] < 0 || slot_tri[k] >= s->n_tris || seen[(size_t)slot_tri[k]]) {
+            rt2h::set_error("rt2_scene_set_slot_order: slot_tri must be a permutation of the triangle indices");
+            return -1;
+        }
+        seen[(size_t)slot_tri[k]] = 1;
+    }
+    if (!cluster_table_covers(t, ng)) {
+        rt2h::set_error("rt2_scene_set_slot_order: the ranges must be contiguous and cover the scene's groups");
+        return -1;
+    }
+    HIPCHECK(hipSetDevice(s->device));
+    HIPCHECK(hipDeviceSynchronize());
+    s->slot_tri.assign(slot_tri, slot_tri + s->n_tris);
+    s->slot_table = *t;
+    return build_slot_image(s);
 }
 
 // Not in rt2.h (test hook): the matrix filter's terms on the hardware

@@ -230,6 +230,27 @@ __device__ __forceinline__ void mt_exact(const MtQ& q, int idx, float& best, int
     }
 }
 
+// mt_exact for triangles visited in slot order (MfmaSpec::slot_order): `slot`
+// and bi are slots, slot_tri[s] the index of slot s's triangle.  The result
+// is the lexicographic minimum of (dst, index) over the accepted pairs, which
+// is what the ascending strict `dst < best` scan leaves; the lookup sits
+// behind dst == best.
+__device__ __forceinline__ void mt_exact_slot(const MtQ& q, int slot, const int* slot_tri, float& best, int& bi,
+                                              float& bestK) {
+    if (!((q.det < 1e-10f && q.det > -1e-10f) || q.det < 0.0f)) {
+        const float inv = 1.0f / q.det;
+        const float dst = q.tnum * inv;
+        const float u = -q.U * inv;
+        const float v = q.V * inv;
+        if (!(dst <= 1e-6f) && !(u < 0.0f || v < 0.0f || 1.0f - u - v < 0.0f) && dst <= best) {
+            if (dst == best && (bi < 0 || slot_tri[slot] > slot_tri[bi])) return;
+            best = dst;
+            bi = slot;
+            bestK = best * 1.0009765625f;
+        }
+    }
+}
+
 // Masked two-phase sweep: phase 1 computes the intermediates and the filter of
 // G triangles (the G predicates stay wave lane-masks in SGPR pairs, no
 // per-lane bit packing); phase 2 runs mt_exact under each mask in index order

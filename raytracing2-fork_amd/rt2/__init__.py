@@ -302,6 +302,8 @@ def lib() -> C.CDLL:
         "rt2_cluster_table_build": (C.c_int, [P, I32, P]),
         "rt2_cluster_need": (C.c_int, [P, P, I64, P]),
         "rt2_scene_set_clusters": (C.c_int, [P, P]),
+        "rt2_cluster_order_build": (C.c_int, [P, I32, P, P]),
+        "rt2_scene_set_slot_order": (C.c_int, [P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -758,7 +760,8 @@ class Scene:
         """A derived device array of the scene (rt2_scene_export, test hook): 0 =
         pre-transformed triangles, 1/2 = render_mfma records/tau, 3/4 = sweep_k16 records/tau,
         5 = the k5 form's per-triangle m.z residual bounds (float32 pairs), 6 = the kthr records (threshold in
-        the K-slots), 7 = the cluster table (one CLUSTER_TABLE_DTYPE record)."""
+        the K-slots), 7 = the cluster table (one CLUSTER_TABLE_DTYPE record), 8 = the slot table of the resident
+        kernel's slot image (one CLUSTER_TABLE_DTYPE record), 9 = its slot_tri (int32 per triangle)."""
         n = lib().rt2_scene_export(self._p, what, None, 0)
         if n < 0:
             raise RT2Error("rt2_scene_export: bad argument")
@@ -776,6 +779,23 @@ class Scene:
         t = np.zeros(1, dtype=CLUSTER_TABLE_DTYPE)
         t[0] = table
         _check(lib().rt2_scene_set_clusters(self._p, t.ctypes.data), "rt2_scene_set_clusters")
+
+    def slot_table(self) -> np.ndarray:
+        """The table over the slot groups of the resident kernel's slot image (rt2_scene_export selector 8)."""
+        return self.export(8, CLUSTER_TABLE_DTYPE)[0]
+
+    def slot_tri(self) -> np.ndarray:
+        """The slot order (rt2_scene_export selector 9): slot s holds triangle slot_tri[s]."""
+        return self.export(9, np.int32)
+
+    def set_slot_order(self, slot_tri, table) -> None:
+        """Installs an explicit slot order and its table (rt2_scene_set_slot_order, test hook)."""
+        st = np.ascontiguousarray(slot_tri, dtype=np.int32)
+        if len(st) != self.n_tris:
+            raise RT2Error("set_slot_order: one slot per triangle")
+        t = np.zeros(1, dtype=CLUSTER_TABLE_DTYPE)
+        t[0] = table
+        _check(lib().rt2_scene_set_slot_order(self._p, st.ctypes.data, t.ctypes.data), "rt2_scene_set_slot_order")
 
     def mfma_probe(self, layout: int, rays: np.ndarray):
         """The matrix filter's terms on the device (rt2_mfma_probe, test hook):
@@ -829,6 +849,19 @@ def cluster_table(triangles: np.ndarray) -> np.ndarray:
     if lib().rt2_cluster_table_build(triangles.ctypes.data, len(triangles), t.ctypes.data) < 0:
         raise RT2Error(f"rt2_cluster_table_build: {lib().rt2_last_error().decode()}")
     return t[0]
+
+
+def cluster_order(triangles: np.ndarray):
+    """The slot order rt2_scene_create derives for a triangle list of at most 38
+    groups (rt2_cluster_order_build, host only): (slot_tri int32 [n], the table
+    over the slot groups).  The identity with rt2_cluster_table_build's table
+    where the rule's own order does not project cheaper."""
+    triangles = np.ascontiguousarray(triangles, dtype=TRI_DTYPE)
+    st = np.zeros(len(triangles), dtype=np.int32)
+    t = np.zeros(1, dtype=CLUSTER_TABLE_DTYPE)
+    if lib().rt2_cluster_order_build(triangles.ctypes.data, len(triangles), st.ctypes.data, t.ctypes.data) < 0:
+        raise RT2Error(f"rt2_cluster_order_build: {lib().rt2_last_error().decode()}")
+    return st, t[0]
 
 
 def cluster_need(table, o: np.ndarray, d: np.ndarray) -> np.ndarray:
