@@ -363,6 +363,58 @@ int rt2_camera_rays(rt2_scene* scene, const rt2_uniforms* uniforms, rt2_shard sh
 int rt2_camera_rays_host(rt2_scene* scene, const rt2_uniforms* uniforms, rt2_shard shard, rt2_ray* rays);
 
 /* ------------------------------------------------------------------------
+ * (1a''') Preview shading queries: traceBasic for a caller's rays
+ *
+ * out[i].rgb is what the reference's preview shader traceBasic (compute.glsl:
+ * 565-645) returns for Ray(o_i, d_i) over the scene as uploaded, with
+ * insideGlass = false at the start, evaluated exactly as the preview render
+ * (rt2_render with basicShading != 0) evaluates it: up to max_bounce segments
+ * through mirrors, glass and the pass-through highlight type; a colour from
+ * diffuse, checker, texture, light and sky; with `shadow` set, one shadow ray
+ * from a diffuse, checker or texture end towards `light`.  No RNG.
+ *   - d is used as given and is not normalised (rt2_camera_rays gives the
+ *     preview's own normalised directions);
+ *   - out[i].segments is the number of closest-hit searches the ray cost, the
+ *     bounces plus the shadow ray: what the preview render adds to the scene's
+ *     segment counter per pixel and frame;
+ *   - rt2_ray.tmax is NOT used, unlike in every other query: each segment of
+ *     traceBasic is unbounded, so the output does not depend on the field;
+ *   - numTextures follows the rule of rt2_surface_rays: the number of images
+ *     given to rt2_scene_set_textures, at most 5;
+ *   - RT2_TRAVERSAL_BRUTE and _BVH have the closest-hit queries' meaning, for
+ *     the bounce segments and for the shadow ray alike;
+ *   - o and d may be any floats.  A non-finite component gives that ray what
+ *     the preview's arithmetic gives and does not disturb the other rays.
+ * rt2_shade_rays reads d_rays and writes d_out in DEVICE memory (n records
+ * each, both aligned to 16 bytes), nothing outside records [0, n), and is
+ * asynchronous on `stream`; its ordering against the scene's other launches is
+ * rt2_trace_rays'.  n == 0 returns 0 and launches nothing.  Bad arguments (a
+ * null scene or opts, n < 0, a null or misaligned pointer with n > 0, non-zero
+ * pad, max_bounce outside 1 .. 256, unknown flag bits, BVH traversal on a
+ * scene without nodes) return < 0 before any device call.
+ * rt2_scene_stats: segments grows by the sum of out[i].segments.  Brute force:
+ * tests is the nominal segments * N.  BVH: tests and node_visits count what
+ * the walks did, the shadow rays' included (leaf tests and nodes popped).
+ * flags: RT2_TRACE_AUTO and RT2_TRACE_SCALAR, with the meaning they have for
+ * rt2_trace_rays.  Every choice gives the same bytes.
+ * rt2_shade_rays_host is the blocking form over host arrays (no alignment
+ * requirement): its device staging buffers are kept by the scene between
+ * calls and freed by rt2_scene_destroy.
+ * ---------------------------------------------------------------------- */
+typedef struct rt2_shade_opts {   /* 32 B */
+    float   light[3];    /* basicShadingLightPosition.xyz */
+    int32_t shadow;      /* basicShadingShadow: 0 = none, non-zero = shadow ray */
+    int32_t max_bounce;  /* maxBounceCount, 1 .. 256 */
+    int32_t pad[3];      /* must be 0 */
+} rt2_shade_opts;
+typedef struct rt2_shaded { float rgb[3]; int32_t segments; } rt2_shaded;   /* 16 B, one store */
+
+int rt2_shade_rays(rt2_scene* scene, const rt2_ray* d_rays, int64_t n, const rt2_shade_opts* opts,
+                   rt2_shaded* d_out, int flags, void* stream);
+int rt2_shade_rays_host(rt2_scene* scene, const rt2_ray* rays, int64_t n, const rt2_shade_opts* opts,
+                        rt2_shaded* out, int flags);
+
+/* ------------------------------------------------------------------------
  * (1b) Multi-GPU: row-tile shards + one RCCL gather
  *
  * The reference renders on one GPU and reads the framebuffer back with

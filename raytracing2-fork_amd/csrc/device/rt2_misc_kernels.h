@@ -13,12 +13,13 @@ namespace {
 // ---------------------------------------------------------------------------
 template <int BLOCK, bool BVH>
 __device__ __forceinline__ void closest_any(const RenderParams& p, const f3& o, const f3& d, int* stack, float& best,
-                                            int& bi, uint32_t& tests) {
+                                            int& bi, uint32_t& tests, uint32_t* node_visits = nullptr) {
     best = 1e38f;
     bi = -1;
     if constexpr (BVH) {
         uint32_t visits = 0;
         closest_bvh<BLOCK>(o, d, p.nodes, p.tri, stack, p.stack_slots, best, bi, tests, visits);
+        if (node_visits) *node_visits += visits;  // rt2_shade_rays counts them; the preview render does not
     } else {
         float bestK = 1e38f * 1.0009765625f;
         sweep_masked<8, true>(o, d, nullptr, (const float*)p.tri, p.n_tris, 0, best, bi, bestK);
@@ -27,7 +28,7 @@ __device__ __forceinline__ void closest_any(const RenderParams& p, const f3& o, 
 
 template <int BLOCK, bool BVH>
 __device__ __forceinline__ f3 trace_basic(const RenderParams& p, f3 o, f3 d, int* stack, uint32_t& segs,
-                                          uint32_t& tests) {
+                                          uint32_t& tests, uint32_t* node_visits = nullptr) {
     f3 cum = mk(0.0f, 0.0f, 0.0f);
     bool inside = false;  // `Ray ray;` leaves insideGlass undefined (:674); false here and in the oracle
     int bc = 0;
@@ -36,7 +37,7 @@ __device__ __forceinline__ f3 trace_basic(const RenderParams& p, f3 o, f3 d, int
         segs++;
         float best;
         int bi;
-        closest_any<BLOCK, BVH>(p, o, d, stack, best, bi, tests);
+        closest_any<BLOCK, BVH>(p, o, d, stack, best, bi, tests, node_visits);
         if (bi < 0) {
             cum = add(cum, sky(d));
             break;
@@ -77,7 +78,7 @@ __device__ __forceinline__ f3 trace_basic(const RenderParams& p, f3 o, f3 d, int
                 segs++;
                 float b2;
                 int bi2;
-                closest_any<BLOCK, BVH>(p, o, toLight, stack, b2, bi2, tests);
+                closest_any<BLOCK, BVH>(p, o, toLight, stack, b2, bi2, tests, node_visits);
                 return divs(bi2 >= 0 ? divs(cum, 5.0f) : cum, (float)bc);
             }
             return divs(cum, (float)bc);

@@ -48,6 +48,7 @@ using namespace rt2d;
 #include "rt2_query.h"
 #include "rt2_occluded.h"
 #include "rt2_surface.h"
+#include "rt2_shade.h"
 
 /* =========================================================================
  * C-ABI, device half
@@ -143,6 +144,10 @@ struct rt2_scene {
     rt2_ray* d_surface_rays = nullptr;
     rt2_surface* d_surface_out = nullptr;
     size_t surface_rays_cap = 0, surface_out_cap = 0;  // records each buffer holds
+    // rt2_shade_rays_host: staging buffers, kept like the above
+    rt2_ray* d_shade_rays = nullptr;
+    rt2_shaded* d_shade_out = nullptr;
+    size_t shade_rays_cap = 0, shade_out_cap = 0;      // records each buffer holds
     unsigned long long* d_region_ctr = nullptr;  // 8 item-region counters, 128 B apart
     unsigned long long* wave_log = nullptr;  // diagnostic wave timeline (rt2_scene_set_wave_log)
     uint32_t wave_log_n = 0;
@@ -583,6 +588,8 @@ extern "C" void rt2_scene_destroy(rt2_scene* s) {
     (void)hipFree(s->d_occluded_out);
     (void)hipFree(s->d_surface_rays);
     (void)hipFree(s->d_surface_out);
+    (void)hipFree(s->d_shade_rays);
+    (void)hipFree(s->d_shade_out);
     (void)hipFree(s->d_region_ctr);
     if (s->host_stream) (void)hipStreamDestroy(s->host_stream);
     delete s;
@@ -1820,6 +1827,121 @@ extern "C" int rt2_camera_rays_host(rt2_scene* s, const rt2_uniforms* u, rt2_sha
     if (surface_staging(s, s->d_surface_rays, s->surface_rays_cap, (size_t)n) != 0) return -1;
     if (rt2_camera_rays(s, u, sh, s->d_surface_rays, st) != 0) return -1;
     HIPCHECK(hipMemcpyAsync(rays, s->d_surface_rays, (size_t)n * sizeof(rt2_ray), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+/* -------------------------------------------------------------------------
+ * Preview shading queries (rt2_shade.h)
+ * ----------------------------------------------------------------------- */
+namespace {
+// after the surface queries' codes: what rt2_scene_diag reports as the variant last launched
+enum : int { H_RES = -14, H_RES_L2 = -15, H_SCALAR = -16, H_BVH = -17 };
+
+// The argument checks of both shading entry points (`device`: the pointers' alignment too).
+int shade_rays_args(const char* who, const rt2_scene* s, const void* rays, int64_t n, const rt2_shade_opts* o,
+                    const void* out, int flags, bool device) {
+    const bool bad_ptr = n > 0 && (!rays || !out);
+    const bool misaligned = device && ((reinterpret_cast<uintptr_t>(rays) & 15) || (reinterpret_cast<uintptr_t>(out) & 15));
+    if (!s || !o || n < 0 || bad_ptr || misaligned || (flags & ~RT2_TRACE_SCALAR) || o->pad[0] || o->pad[1] ||
+        o->pad[2] || o->max_bounce < 1 || o->max_bounce > 256) {
+        rt2h::set_error(std::string(who) + ": bad argument (a scene and options, n >= 0, " +
+                        (device ? "rays and records aligned to 16 B, " : "rays and records, ") +
+                        "pad 0, max_bounce in 1 .. 256, flags 0 or RT2_TRACE_SCALAR)");
+        return -1;
+    }
+    if (n > 0 && s->traversal == RT2_TRAVERSAL_BVH && s->n_nodes == 0) {
+        rt2h::set_error(std::string(who) + ": bad argument (BVH traversal needs the node array)");
+        return -1;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" int rt2_shade_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, const rt2_shade_opts* opts,
+                              rt2_shaded* d_out, int flags, void* stream) {
+    if (shade_rays_args("rt2_shade_rays", s, d_rays, n, opts, d_out, flags, true) != 0) return -1;
+    if (n == 0) return 0;
+    const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
+    HIPCHECK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.tri = s->d_tri;
+    p.n_tris = s->n_tris;
+    p.mfma_A = s->mfma_A;
+    p.mfma_kt_frag = s->d_mfma_kt;
+    p.nodes = s->d_nodes;
+    p.stack_slots = s->bvh_depth + 2;
+    p.item_counter = s->d_counters;
+    p.seg_counter = s->d_counters + 1;
+    // what trace_basic and shade_step read
+    p.unit_n = s->d_unit_n;
+    p.tri_mtl = s->d_mtl;
+    p.mats = s->d_mats;
+    p.n_mats = s->n_mats;
+    p.raw = s->d_raw;
+    p.texels = s->d_texels;
+    p.tex_desc = s->d_tex_desc;
+    p.n_tex = s->n_tex;
+    p.num_textures = std::min(s->n_tex, 5);  // the rule of rt2_surface_rays: the images bound, at most the five units
+    p.maxBounce = opts->max_bounce;
+    p.basicShadow = opts->shadow;
+    p.light[0] = opts->light[0];
+    p.light[1] = opts->light[1];
+    p.light[2] = opts->light[2];
+    ShadeParams q{d_rays, d_out, (long long)n};
+    // RT2_TRACE_AUTO: the matrix kernel at every ray count, the choice of rt2_trace_rays.  On config B it beat the
+    // scalar kernel in every round from 2^22 rays (0.83 against 4.99 ms with the shadow ray) down to one 64-ray chunk
+    // (52 against 289 us; profiles/shade_ab.json).
+    const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
+    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
+    if (matrix) {
+        const unsigned blocks = (unsigned)std::min<long long>(s->num_cus, (n + 1023) / 1024);
+        const bool resident = (s->n_tris + 31) / 32 <= kResGroups;
+        if (resident)
+            hipLaunchKernelGGL(shade_rays_k5r<kOccRes>, dim3(blocks), dim3(kOccRes.m.block), 0, st, p, q);
+        else
+            hipLaunchKernelGGL(shade_rays_k5r<kOccResL2>, dim3(blocks), dim3(kOccResL2.m.block), 0, st, p, q);
+        HIPCHECK(hipGetLastError());
+        s->last_kind = K_MFMA;
+        s->last_variant = resident ? H_RES : H_RES_L2;
+    } else {
+        for (long long i0 = 0; i0 < (long long)n; i0 += kQuerySlice) {
+            q.rays = d_rays + i0;
+            q.out = d_out + i0;
+            q.n = std::min<long long>(kQuerySlice, (long long)n - i0);
+            const unsigned blocks = (unsigned)((q.n + kQueryBlock - 1) / kQueryBlock);
+            if (bvh)
+                hipLaunchKernelGGL((shade_rays_scalar<kQueryBlock, true>), dim3(blocks), dim3(kQueryBlock),
+                                   (size_t)p.stack_slots * kQueryBlock * sizeof(int), st, p, q);
+            else
+                hipLaunchKernelGGL((shade_rays_scalar<kQueryBlock, false>), dim3(blocks), dim3(kQueryBlock), 0, st, p,
+                                   q);
+            HIPCHECK(hipGetLastError());
+        }
+        s->last_kind = bvh ? K_BVH : K_SMEM;
+        s->last_variant = bvh ? H_BVH : H_SCALAR;
+    }
+    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(s->last_launch, st));
+    s->last_launch_valid = true;
+    s->tests_per_seg = (unsigned long long)s->n_tris;
+    return 0;
+}
+
+extern "C" int rt2_shade_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n, const rt2_shade_opts* opts,
+                                   rt2_shaded* out, int flags) {
+    if (shade_rays_args("rt2_shade_rays_host", s, rays, n, opts, out, flags, false) != 0) return -1;
+    if (n == 0) return 0;
+    HIPCHECK(hipSetDevice(s->device));
+    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    hipStream_t st = s->host_stream;
+    if (surface_staging(s, s->d_shade_rays, s->shade_rays_cap, (size_t)n) != 0) return -1;
+    if (surface_staging(s, s->d_shade_out, s->shade_out_cap, (size_t)n) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(s->d_shade_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
+    if (rt2_shade_rays(s, s->d_shade_rays, n, opts, s->d_shade_out, flags, st) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(out, s->d_shade_out, (size_t)n * sizeof(rt2_shaded), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     return 0;
 }

@@ -134,6 +134,10 @@ class Stats(C.Structure):
                 ("node_visits", C.c_uint64)]
 
 
+class ShadeOpts(C.Structure):  # rt2_shade_opts
+    _fields_ = [("light", C.c_float * 3), ("shadow", C.c_int32), ("max_bounce", C.c_int32), ("pad", C.c_int32 * 3)]
+
+
 class CameraDesc(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("position", C.c_float * 3), ("hfov", C.c_float),
                 ("pitch", C.c_float), ("yaw", C.c_float), ("focus_distance", C.c_float),
@@ -141,7 +145,7 @@ class CameraDesc(C.Structure):
 
 
 assert C.sizeof(Triangle) == 80 and C.sizeof(Material) == 96
-assert C.sizeof(Node) == 48 and C.sizeof(Uniforms) == 192
+assert C.sizeof(Node) == 48 and C.sizeof(Uniforms) == 192 and C.sizeof(ShadeOpts) == 32
 
 TRI_DTYPE = np.dtype([("a", "<f4", 4), ("b", "<f4", 4), ("c", "<f4", 4), ("aTex", "<f4", 2), ("bTex", "<f4", 2),
                       ("cTex", "<f4", 2), ("materialIndex", "<i4"), ("pad", "<f4")])
@@ -172,6 +176,10 @@ assert CLUSTER_DTYPE.itemsize == 32 and CLUSTER_TABLE_DTYPE.itemsize == 32 + 32 
 QUERY_RES, QUERY_RES_L2, QUERY_SCALAR, QUERY_BVH = -2, -3, -4, -5  # Scene.last_kernel after a query
 OCCLUDED_RES, OCCLUDED_RES_L2, OCCLUDED_SCALAR, OCCLUDED_BVH = -6, -7, -8, -9  # ... after an occlusion query
 SURFACE_RES, SURFACE_RES_L2, SURFACE_SCALAR, SURFACE_BVH = -10, -11, -12, -13  # ... after a surface query
+SHADE_RES, SHADE_RES_L2, SHADE_SCALAR, SHADE_BVH = -14, -15, -16, -17  # ... after a preview shading query
+# rt2_shaded (preview shading queries): traceBasic's colour and the closest-hit searches the ray cost
+SHADED_DTYPE = np.dtype([("rgb", "<f4", 3), ("segments", "<i4")])
+assert SHADED_DTYPE.itemsize == 16
 
 # Every symbol include/rt2.h declares (tests check the library exports them all).
 EXPORTED = [
@@ -190,6 +198,7 @@ EXPORTED = [
     "rt2_comm_size", "rt2_comm_check", "rt2_gather_slabs", "rt2_unshard_slabs", "rt2_render_host_gather",
     "rt2_comm_wait", "rt2_trace_rays", "rt2_trace_rays_host", "rt2_occluded", "rt2_occluded_host",
     "rt2_surface_rays", "rt2_surface_rays_host", "rt2_camera_rays", "rt2_camera_rays_host",
+    "rt2_shade_rays", "rt2_shade_rays_host",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -235,6 +244,8 @@ def lib() -> C.CDLL:
         "rt2_occluded_host": (C.c_int, [P, P, I64, P, C.c_int]),
         "rt2_surface_rays": (C.c_int, [P, P, I64, P, C.c_int, P]),
         "rt2_surface_rays_host": (C.c_int, [P, P, I64, P, C.c_int]),
+        "rt2_shade_rays": (C.c_int, [P, P, I64, C.POINTER(ShadeOpts), P, C.c_int, P]),
+        "rt2_shade_rays_host": (C.c_int, [P, P, I64, C.POINTER(ShadeOpts), P, C.c_int]),
         "rt2_camera_rays": (C.c_int, [P, C.POINTER(Uniforms), Shard, P, P]),
         "rt2_camera_rays_host": (C.c_int, [P, C.POINTER(Uniforms), Shard, P]),
         "rt2_resolve_rgba32f": (C.c_int, [P, I64, U32, P, P]),
@@ -464,6 +475,14 @@ def offline_uniforms(width, height, max_bounce, rays_per_pixel, num_triangles, n
     u = Uniforms()
     lib().rt2_uniforms_offline(C.byref(u), width, height, max_bounce, rays_per_pixel, num_triangles, num_textures)
     return u
+
+
+def shade_opts(light=(0.0, 0.0, 0.0), shadow: bool = False, max_bounce: int = 1) -> ShadeOpts:
+    """rt2_shade_opts: the preview's light position, shadow switch and bounce limit."""
+    o = ShadeOpts()
+    o.light[:] = [float(x) for x in light]
+    o.shadow, o.max_bounce = int(bool(shadow)), int(max_bounce)
+    return o
 
 
 def shard(tile_rows=1, rank=0, nranks=1) -> Shard:
@@ -745,12 +764,73 @@ class Scene:
                 "albedo": rec["albedo"].reshape(shape + (3,)).copy(),
                 "uv": np.stack([rec["u"], rec["v"]], -1).reshape(shape + (2,))}
 
+    def shade_rays(self, origins, directions, light=(0.0, 0.0, 0.0), shadow: bool = False, max_bounce: int = 1,
+                   flags: int = 0) -> np.ndarray:
+        """The preview shader's colour of n rays (rt2_shade_rays_host, blocking):
+        origins and directions (n, 3), used as given; `light`, `shadow` and
+        `max_bounce` are the uniforms' basicShadingLightPosition,
+        basicShadingShadow and maxBounceCount.  Returns a SHADED_DTYPE array:
+        rgb is what traceBasic returns for the ray, segments the closest-hit
+        searches it cost (bounces plus the shadow ray).  Every segment is
+        unbounded: there is no tmax."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise RT2Error(f"shade_rays: {len(o)} origins for {len(d)} directions")
+        rays = np.zeros(len(o), dtype=RAY_DTYPE)
+        rays["o"], rays["d"] = o, d
+        out = np.zeros(len(o), dtype=SHADED_DTYPE)
+        opts = shade_opts(light, shadow, max_bounce)
+        _check(lib().rt2_shade_rays_host(self._p, rays.ctypes.data, len(rays), C.byref(opts), out.ctypes.data,
+                                         int(flags)), "rt2_shade_rays_host")
+        return out
+
+    def shade_rays_device(self, rays_ptr: int, n: int, out_ptr: int, light=(0.0, 0.0, 0.0), shadow: bool = False,
+                          max_bounce: int = 1, flags: int = 0, stream: int = 0) -> None:
+        """Asynchronous shading query over device arrays of n rt2_ray / rt2_shaded records (rt2_shade_rays)."""
+        opts = shade_opts(light, shadow, max_bounce)
+        _check(lib().rt2_shade_rays(self._p, C.c_void_p(rays_ptr) if rays_ptr else None, int(n), C.byref(opts),
+                                    C.c_void_p(out_ptr) if out_ptr else None, int(flags),
+                                    C.c_void_p(stream) if stream else None), "rt2_shade_rays")
+
+    def preview(self, u: Uniforms, sh: Optional[Shard] = None, flags: int = 0) -> np.ndarray:
+        """The preview image of a view through the shading query: the slab's
+        camera rays are written into a device buffer and shaded on the same
+        stream with the uniforms' basicShadingLightPosition,
+        basicShadingShadow and maxBounceCount.  Returns (rows, W, 4) float32
+        with alpha 1: the bits of render_host(u with basicShading = 1, 0, 1),
+        when u.numTextures is the number of images given to set_textures (at
+        most 5), which is what a ray query takes."""
+        import torch
+
+        sh = sh or shard()
+        rows = shard_rows(u.height, sh)
+        if rows < 0:
+            raise RT2Error("preview: bad shard")
+        W = int(u.width)
+        n = rows * W
+        img = np.ones((rows, W, 4), dtype=np.float32)
+        if n:
+            lp = u.basicShadingLightPosition
+            dev = torch.device("cuda", self.device)
+            with torch.cuda.device(dev):
+                rays = torch.empty(n * RAY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                out = torch.empty(n * SHADED_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                self.camera_rays_device(u, sh, rays.data_ptr(), stream)
+                self.shade_rays_device(rays.data_ptr(), n, out.data_ptr(), (lp.x, lp.y, lp.z),
+                                       bool(u.basicShadingShadow), int(u.maxBounceCount), flags, stream)
+                rec = out.cpu().numpy().view(SHADED_DTYPE)  # the copy waits for the stream
+            img[..., :3] = rec["rgb"].reshape(rows, W, 3)
+        return img
+
     def last_kernel(self) -> int:
         """What the scene launched last (rt2_scene_diag): a render's variant id (-1: the traceBasic preview), or
         after a query QUERY_RES (trace_rays_k5r, every group resident), QUERY_RES_L2 (its L2 continuation),
         QUERY_SCALAR or QUERY_BVH (trace_rays_scalar); after an occlusion query OCCLUDED_RES, OCCLUDED_RES_L2
         (occluded_k5r), OCCLUDED_SCALAR or OCCLUDED_BVH (occluded_scalar); after a surface query SURFACE_RES,
-        SURFACE_RES_L2 (surface_k5r), SURFACE_SCALAR or SURFACE_BVH (surface_scalar)."""
+        SURFACE_RES_L2 (surface_k5r), SURFACE_SCALAR or SURFACE_BVH (surface_scalar); after a preview shading query
+        SHADE_RES, SHADE_RES_L2 (shade_rays_k5r), SHADE_SCALAR or SHADE_BVH (shade_rays_scalar)."""
         c, v = (C.c_ulonglong * 8)(), C.c_int(-1)
         if lib().rt2_scene_diag(self._p, c, C.byref(v)) != 0:
             raise RT2Error("rt2_scene_diag failed")
