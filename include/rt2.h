@@ -415,6 +415,80 @@ int rt2_shade_rays_host(rt2_scene* scene, const rt2_ray* rays, int64_t n, const 
                         rt2_shaded* out, int flags);
 
 /* ------------------------------------------------------------------------
+ * (1a'''') Radiance queries: the path tracer's trace() for a caller's rays
+ *
+ * out[i].rgb is what the reference's Monte-Carlo path tracer trace()
+ * (compute.glsl:472-563) returns for Ray(o_i, d_i, insideGlass = false) with
+ * rngState = rng[i] over the scene as uploaded, maxBounceCount and
+ * environmentalLight taken from opts, evaluated exactly as rt2_render
+ * evaluates it: the scatter on diffuse, texture, specular, checker and glass,
+ * the return on a light, magenta for every other type (GLASS_HIGHLIGHT
+ * included), the isEdgeHighlight pass-through after the first bounce, the
+ * roulette, and the sky on a miss when environmental_light is set.  It is the
+ * value the render adds to colorCumulative (:692): linear, before the mean
+ * over numRaysPerPixel, the tonemap and the sRGB encoding.
+ *   - on return rng[i] holds the stream's state after the path's last draw:
+ *     what `seed` holds after trace(rayJittered, seed), so a caller can go on
+ *     drawing from it;
+ *   - out[i].segments is the number of closest-hit searches: the bounces
+ *     traced;
+ *   - d is used as given and is not normalised;
+ *   - rt2_ray.tmax is NOT used, as in rt2_shade_rays: every segment of trace
+ *     is unbounded;
+ *   - numTextures follows the rule of rt2_surface_rays;
+ *   - RT2_TRAVERSAL_BRUTE and _BVH have the closest-hit queries' meaning;
+ *   - o and d may be any floats.  A non-finite component gives that ray what
+ *     the render's arithmetic gives and does not disturb the other rays.
+ * rt2_radiance_rays reads d_rays, reads and writes d_rng and writes d_out in
+ * DEVICE memory (n records each; rays and records aligned to 16 bytes, rng to
+ * 4), nothing outside records [0, n), and is asynchronous on `stream`; its
+ * ordering against the scene's other launches is rt2_trace_rays'.  n == 0
+ * returns 0 and launches nothing.  Bad arguments (a null scene or opts, n < 0,
+ * a null or misaligned pointer with n > 0, non-zero pad, max_bounce outside
+ * 1 .. 256, unknown flag bits, BVH traversal on a scene without nodes) return
+ * < 0 before any device call.
+ * rt2_scene_stats: segments grows by the sum of out[i].segments.  Brute force:
+ * tests is the nominal segments * N.  BVH: tests and node_visits count what
+ * the walks did.
+ * flags: RT2_TRACE_AUTO and RT2_TRACE_SCALAR, with the meaning they have for
+ * rt2_trace_rays.  Every choice gives the same bytes.
+ * rt2_radiance_rays_host is the blocking form over host arrays (no alignment
+ * requirement; rng is copied in and out): its device staging buffers are kept
+ * by the scene between calls and freed by rt2_scene_destroy.
+ *
+ * rt2_path_rays is the path tracer's camera: for every pixel of the shard's
+ * slab, in slab-row order (rt2_shard_rows(height, shard) * width records), it
+ * sets rng[i] = x + y * width + frame_index * 968824447u (compute.glsl:668,
+ * 32-bit) when reseed != 0 and uses rng[i] as found otherwise, then executes
+ * compute.glsl:686-690 as the render does: one draw for the defocus-disk
+ * angle (with the pinned cos and sin), two jitter draws, o = cameraPos +
+ * defocusDiskRight * cos + defocusDiskUp * sin, d = normalize(endPointJittered
+ * - o), tmax = 0 and pad = 0; rng[i] is left at the state after those three
+ * draws.  Alternating rt2_path_rays (reseed on the first sample only) and
+ * rt2_radiance_rays numRaysPerPixel times reproduces the render's per-pixel
+ * sample sequence exactly.  One small launch, asynchronous on `stream`; it
+ * reads nothing of the scene but its device and does not count in
+ * rt2_scene_stats.  Bad arguments are rt2_camera_rays' and a null or
+ * misaligned d_rng for a non-empty slab.  rt2_path_rays_host is the blocking
+ * form over host arrays.
+ * ---------------------------------------------------------------------- */
+typedef struct rt2_path_opts {   /* 16 B */
+    int32_t max_bounce;           /* maxBounceCount, 1 .. 256 */
+    int32_t environmental_light;  /* environmentalLight: 0 = black sky */
+    int32_t pad[2];               /* must be 0 */
+} rt2_path_opts;
+typedef struct rt2_radiance { float rgb[3]; int32_t segments; } rt2_radiance;   /* 16 B, one store */
+
+int rt2_radiance_rays(rt2_scene* scene, const rt2_ray* d_rays, int64_t n, const rt2_path_opts* opts,
+                      uint32_t* d_rng, rt2_radiance* d_out, int flags, void* stream);
+int rt2_radiance_rays_host(rt2_scene* scene, const rt2_ray* rays, int64_t n, const rt2_path_opts* opts,
+                           uint32_t* rng, rt2_radiance* out, int flags);
+int rt2_path_rays(rt2_scene* scene, const rt2_uniforms* uniforms, rt2_shard shard, uint32_t frame_index, int reseed,
+                  uint32_t* d_rng, rt2_ray* d_rays, void* stream);
+int rt2_path_rays_host(rt2_scene* scene, const rt2_uniforms* uniforms, rt2_shard shard, uint32_t frame_index,
+                       int reseed, uint32_t* rng, rt2_ray* rays);
+
+/* ------------------------------------------------------------------------
  * (1b) Multi-GPU: row-tile shards + one RCCL gather
  *
  * The reference renders on one GPU and reads the framebuffer back with

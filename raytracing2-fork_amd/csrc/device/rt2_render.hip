@@ -49,6 +49,7 @@ using namespace rt2d;
 #include "rt2_occluded.h"
 #include "rt2_surface.h"
 #include "rt2_shade.h"
+#include "rt2_radiance.h"
 
 /* =========================================================================
  * C-ABI, device half
@@ -148,6 +149,11 @@ struct rt2_scene {
     rt2_ray* d_shade_rays = nullptr;
     rt2_shaded* d_shade_out = nullptr;
     size_t shade_rays_cap = 0, shade_out_cap = 0;      // records each buffer holds
+    // rt2_radiance_rays_host / rt2_path_rays_host: staging buffers, kept like the above
+    rt2_ray* d_radiance_rays = nullptr;
+    uint32_t* d_radiance_rng = nullptr;
+    rt2_radiance* d_radiance_out = nullptr;
+    size_t radiance_rays_cap = 0, radiance_rng_cap = 0, radiance_out_cap = 0;  // records each buffer holds
     unsigned long long* d_region_ctr = nullptr;  // 8 item-region counters, 128 B apart
     unsigned long long* wave_log = nullptr;  // diagnostic wave timeline (rt2_scene_set_wave_log)
     uint32_t wave_log_n = 0;
@@ -590,6 +596,9 @@ extern "C" void rt2_scene_destroy(rt2_scene* s) {
     (void)hipFree(s->d_surface_out);
     (void)hipFree(s->d_shade_rays);
     (void)hipFree(s->d_shade_out);
+    (void)hipFree(s->d_radiance_rays);
+    (void)hipFree(s->d_radiance_rng);
+    (void)hipFree(s->d_radiance_out);
     (void)hipFree(s->d_region_ctr);
     if (s->host_stream) (void)hipStreamDestroy(s->host_stream);
     delete s;
@@ -1942,6 +1951,190 @@ extern "C" int rt2_shade_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n,
     HIPCHECK(hipMemcpyAsync(s->d_shade_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
     if (rt2_shade_rays(s, s->d_shade_rays, n, opts, s->d_shade_out, flags, st) != 0) return -1;
     HIPCHECK(hipMemcpyAsync(out, s->d_shade_out, (size_t)n * sizeof(rt2_shaded), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+/* -------------------------------------------------------------------------
+ * Radiance queries (rt2_radiance.h)
+ * ----------------------------------------------------------------------- */
+namespace {
+// after the shading queries' codes: what rt2_scene_diag reports as the variant last launched
+enum : int { R_RES = -18, R_RES_L2 = -19, R_SCALAR = -20, R_BVH = -21 };
+
+// The argument checks of both radiance entry points (`device`: the pointers' alignment too).
+int radiance_rays_args(const char* who, const rt2_scene* s, const void* rays, int64_t n, const rt2_path_opts* o,
+                       const void* rng, const void* out, int flags, bool device) {
+    const bool bad_ptr = n > 0 && (!rays || !rng || !out);
+    const bool misaligned = device && n > 0 &&
+                            ((reinterpret_cast<uintptr_t>(rays) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) ||
+                             (reinterpret_cast<uintptr_t>(rng) & 3));
+    if (!s || !o || n < 0 || bad_ptr || misaligned || (flags & ~RT2_TRACE_SCALAR) || o->pad[0] || o->pad[1] ||
+        o->max_bounce < 1 || o->max_bounce > 256) {
+        rt2h::set_error(std::string(who) + ": bad argument (a scene and options, n >= 0, " +
+                        (device ? "rays and records aligned to 16 B and rng to 4 B, " : "rays, rng and records, ") +
+                        "pad 0, max_bounce in 1 .. 256, flags 0 or RT2_TRACE_SCALAR)");
+        return -1;
+    }
+    if (n > 0 && s->traversal == RT2_TRAVERSAL_BVH && s->n_nodes == 0) {
+        rt2h::set_error(std::string(who) + ": bad argument (BVH traversal needs the node array)");
+        return -1;
+    }
+    return 0;
+}
+
+// The argument checks of both path-camera entry points: camera_rays_args and the stream array.
+int path_rays_args(const char* who, const rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, const void* rng,
+                   const void* rays, bool device, long long* n) {
+    if (camera_rays_args(who, s, u, sh, rays, device, n) != 0) return -1;
+    if (*n > 0 && (!rng || (device && (reinterpret_cast<uintptr_t>(rng) & 3)))) {
+        rt2h::set_error(std::string(who) + ": bad argument (rng must not be null" +
+                        (device ? ", and aligned to 4 B)" : ")"));
+        return -1;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" int rt2_radiance_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, const rt2_path_opts* opts,
+                                 uint32_t* d_rng, rt2_radiance* d_out, int flags, void* stream) {
+    if (radiance_rays_args("rt2_radiance_rays", s, d_rays, n, opts, d_rng, d_out, flags, true) != 0) return -1;
+    if (n == 0) return 0;
+    const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
+    HIPCHECK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.tri = s->d_tri;
+    p.n_tris = s->n_tris;
+    p.mfma_A = s->mfma_A;
+    p.mfma_kt_frag = s->d_mfma_kt;
+    p.nodes = s->d_nodes;
+    p.stack_slots = s->bvh_depth + 2;
+    p.item_counter = s->d_counters;
+    p.seg_counter = s->d_counters + 1;
+    // what radiance_step reads
+    p.unit_n = s->d_unit_n;
+    p.tri_mtl = s->d_mtl;
+    p.mats = s->d_mats;
+    p.n_mats = s->n_mats;
+    p.raw = s->d_raw;
+    p.texels = s->d_texels;
+    p.tex_desc = s->d_tex_desc;
+    p.n_tex = s->n_tex;
+    p.num_textures = std::min(s->n_tex, 5);  // the rule of rt2_surface_rays: the images bound, at most the five units
+    p.maxBounce = opts->max_bounce;
+    p.envLight = opts->environmental_light;
+    RadianceParams q{d_rays, d_rng, d_out, (long long)n};
+    // RT2_TRACE_AUTO: the matrix kernel at every ray count, the choice of rt2_shade_rays.
+    const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
+    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
+    if (matrix) {
+        const unsigned blocks = (unsigned)std::min<long long>(s->num_cus, (n + 1023) / 1024);
+        const bool resident = (s->n_tris + 31) / 32 <= kResGroups;
+        if (resident)
+            hipLaunchKernelGGL(radiance_rays_k5r<kOccRes>, dim3(blocks), dim3(kOccRes.m.block), 0, st, p, q);
+        else
+            hipLaunchKernelGGL(radiance_rays_k5r<kOccResL2>, dim3(blocks), dim3(kOccResL2.m.block), 0, st, p, q);
+        HIPCHECK(hipGetLastError());
+        s->last_kind = K_MFMA;
+        s->last_variant = resident ? R_RES : R_RES_L2;
+    } else {
+        for (long long i0 = 0; i0 < (long long)n; i0 += kQuerySlice) {
+            q.rays = d_rays + i0;
+            q.rng = d_rng + i0;
+            q.out = d_out + i0;
+            q.n = std::min<long long>(kQuerySlice, (long long)n - i0);
+            const unsigned blocks = (unsigned)((q.n + kQueryBlock - 1) / kQueryBlock);
+            if (bvh)
+                hipLaunchKernelGGL((radiance_rays_scalar<kQueryBlock, true>), dim3(blocks), dim3(kQueryBlock),
+                                   (size_t)p.stack_slots * kQueryBlock * sizeof(int), st, p, q);
+            else
+                hipLaunchKernelGGL((radiance_rays_scalar<kQueryBlock, false>), dim3(blocks), dim3(kQueryBlock), 0, st,
+                                   p, q);
+            HIPCHECK(hipGetLastError());
+        }
+        s->last_kind = bvh ? K_BVH : K_SMEM;
+        s->last_variant = bvh ? R_BVH : R_SCALAR;
+    }
+    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(s->last_launch, st));
+    s->last_launch_valid = true;
+    s->tests_per_seg = (unsigned long long)s->n_tris;
+    return 0;
+}
+
+extern "C" int rt2_radiance_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n, const rt2_path_opts* opts,
+                                      uint32_t* rng, rt2_radiance* out, int flags) {
+    if (radiance_rays_args("rt2_radiance_rays_host", s, rays, n, opts, rng, out, flags, false) != 0) return -1;
+    if (n == 0) return 0;
+    HIPCHECK(hipSetDevice(s->device));
+    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    hipStream_t st = s->host_stream;
+    if (surface_staging(s, s->d_radiance_rays, s->radiance_rays_cap, (size_t)n) != 0) return -1;
+    if (surface_staging(s, s->d_radiance_rng, s->radiance_rng_cap, (size_t)n) != 0) return -1;
+    if (surface_staging(s, s->d_radiance_out, s->radiance_out_cap, (size_t)n) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(s->d_radiance_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(s->d_radiance_rng, rng, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (rt2_radiance_rays(s, s->d_radiance_rays, n, opts, s->d_radiance_rng, s->d_radiance_out, flags, st) != 0)
+        return -1;
+    HIPCHECK(hipMemcpyAsync(out, s->d_radiance_out, (size_t)n * sizeof(rt2_radiance), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(rng, s->d_radiance_rng, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int rt2_path_rays(rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, uint32_t frame_index, int reseed,
+                             uint32_t* d_rng, rt2_ray* d_rays, void* stream) {
+    long long n = 0;
+    if (path_rays_args("rt2_path_rays", s, u, sh, d_rng, d_rays, true, &n) != 0) return -1;
+    if (n == 0) return 0;
+    HIPCHECK(hipSetDevice(s->device));
+    PathRaysParams c;
+    std::memset(&c, 0, sizeof(c));
+    auto cp = [](float* d, const rt2_vec4& v) {
+        d[0] = v.x;
+        d[1] = v.y;
+        d[2] = v.z;
+    };
+    cp(c.cam, u->cameraPos);
+    cp(c.vpRight, u->viewportRight);
+    cp(c.vpUp, u->viewportUp);
+    cp(c.vpFront, u->viewportFront);
+    cp(c.pixR, u->pixelRight);
+    cp(c.pixU, u->pixelUp);
+    cp(c.defR, u->defocusDiskRight);
+    cp(c.defU, u->defocusDiskUp);
+    c.W = (int)u->width;
+    c.H = (int)u->height;
+    c.tile_rows = sh.tile_rows;
+    c.rank = sh.rank;
+    c.nranks = sh.nranks;
+    c.frame = frame_index;
+    c.reseed = reseed;
+    c.n = n;
+    c.rng = d_rng;
+    c.out = d_rays;
+    hipLaunchKernelGGL(path_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int rt2_path_rays_host(rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, uint32_t frame_index,
+                                  int reseed, uint32_t* rng, rt2_ray* rays) {
+    long long n = 0;
+    if (path_rays_args("rt2_path_rays_host", s, u, sh, rng, rays, false, &n) != 0) return -1;
+    if (n == 0) return 0;
+    HIPCHECK(hipSetDevice(s->device));
+    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    hipStream_t st = s->host_stream;
+    if (surface_staging(s, s->d_radiance_rays, s->radiance_rays_cap, (size_t)n) != 0) return -1;
+    if (surface_staging(s, s->d_radiance_rng, s->radiance_rng_cap, (size_t)n) != 0) return -1;
+    if (!reseed)
+        HIPCHECK(hipMemcpyAsync(s->d_radiance_rng, rng, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (rt2_path_rays(s, u, sh, frame_index, reseed, s->d_radiance_rng, s->d_radiance_rays, st) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(rays, s->d_radiance_rays, (size_t)n * sizeof(rt2_ray), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(rng, s->d_radiance_rng, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     return 0;
 }

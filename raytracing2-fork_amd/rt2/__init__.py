@@ -138,6 +138,10 @@ class ShadeOpts(C.Structure):  # rt2_shade_opts
     _fields_ = [("light", C.c_float * 3), ("shadow", C.c_int32), ("max_bounce", C.c_int32), ("pad", C.c_int32 * 3)]
 
 
+class PathOpts(C.Structure):  # rt2_path_opts
+    _fields_ = [("max_bounce", C.c_int32), ("environmental_light", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
 class CameraDesc(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("position", C.c_float * 3), ("hfov", C.c_float),
                 ("pitch", C.c_float), ("yaw", C.c_float), ("focus_distance", C.c_float),
@@ -180,6 +184,10 @@ SHADE_RES, SHADE_RES_L2, SHADE_SCALAR, SHADE_BVH = -14, -15, -16, -17  # ... aft
 # rt2_shaded (preview shading queries): traceBasic's colour and the closest-hit searches the ray cost
 SHADED_DTYPE = np.dtype([("rgb", "<f4", 3), ("segments", "<i4")])
 assert SHADED_DTYPE.itemsize == 16
+RADIANCE_RES, RADIANCE_RES_L2, RADIANCE_SCALAR, RADIANCE_BVH = -18, -19, -20, -21  # ... after a radiance query
+# rt2_radiance (radiance queries): trace()'s linear colour and the closest-hit searches the path cost
+RADIANCE_DTYPE = np.dtype([("rgb", "<f4", 3), ("segments", "<i4")])
+assert RADIANCE_DTYPE.itemsize == 16 and C.sizeof(PathOpts) == 16
 
 # Every symbol include/rt2.h declares (tests check the library exports them all).
 EXPORTED = [
@@ -199,6 +207,7 @@ EXPORTED = [
     "rt2_comm_wait", "rt2_trace_rays", "rt2_trace_rays_host", "rt2_occluded", "rt2_occluded_host",
     "rt2_surface_rays", "rt2_surface_rays_host", "rt2_camera_rays", "rt2_camera_rays_host",
     "rt2_shade_rays", "rt2_shade_rays_host",
+    "rt2_radiance_rays", "rt2_radiance_rays_host", "rt2_path_rays", "rt2_path_rays_host",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -246,6 +255,10 @@ def lib() -> C.CDLL:
         "rt2_surface_rays_host": (C.c_int, [P, P, I64, P, C.c_int]),
         "rt2_shade_rays": (C.c_int, [P, P, I64, C.POINTER(ShadeOpts), P, C.c_int, P]),
         "rt2_shade_rays_host": (C.c_int, [P, P, I64, C.POINTER(ShadeOpts), P, C.c_int]),
+        "rt2_radiance_rays": (C.c_int, [P, P, I64, C.POINTER(PathOpts), P, P, C.c_int, P]),
+        "rt2_radiance_rays_host": (C.c_int, [P, P, I64, C.POINTER(PathOpts), P, P, C.c_int]),
+        "rt2_path_rays": (C.c_int, [P, C.POINTER(Uniforms), Shard, U32, C.c_int, P, P, P]),
+        "rt2_path_rays_host": (C.c_int, [P, C.POINTER(Uniforms), Shard, U32, C.c_int, P, P]),
         "rt2_camera_rays": (C.c_int, [P, C.POINTER(Uniforms), Shard, P, P]),
         "rt2_camera_rays_host": (C.c_int, [P, C.POINTER(Uniforms), Shard, P]),
         "rt2_resolve_rgba32f": (C.c_int, [P, I64, U32, P, P]),
@@ -482,6 +495,13 @@ def shade_opts(light=(0.0, 0.0, 0.0), shadow: bool = False, max_bounce: int = 1)
     o = ShadeOpts()
     o.light[:] = [float(x) for x in light]
     o.shadow, o.max_bounce = int(bool(shadow)), int(max_bounce)
+    return o
+
+
+def path_opts(max_bounce: int = 8, environmental_light: bool = True) -> PathOpts:
+    """rt2_path_opts: the path tracer's bounce limit and sky switch."""
+    o = PathOpts()
+    o.max_bounce, o.environmental_light = int(max_bounce), int(bool(environmental_light))
     return o
 
 
@@ -824,13 +844,120 @@ class Scene:
             img[..., :3] = rec["rgb"].reshape(rows, W, 3)
         return img
 
+    def radiance(self, origins, directions, rng, max_bounce: int = 8, environmental_light: bool = True,
+                 flags: int = 0):
+        """The path tracer's radiance along n rays (rt2_radiance_rays_host,
+        blocking): origins and directions (n, 3), used as given; rng (n,)
+        uint32, one random stream per ray.  Returns (records, rng_out): a
+        RADIANCE_DTYPE array (rgb is what trace() returns for the ray, linear;
+        segments the closest-hit searches the path cost) and the streams'
+        states after the paths' last draws.  The caller's rng array is not
+        modified.  Every segment is unbounded: there is no tmax."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        state = np.array(rng, dtype=np.uint32).reshape(-1)  # a copy
+        if len(o) != len(d) or len(o) != len(state):
+            raise RT2Error(f"radiance: {len(o)} origins, {len(d)} directions, {len(state)} rng states")
+        rays = np.zeros(len(o), dtype=RAY_DTYPE)
+        rays["o"], rays["d"] = o, d
+        out = np.zeros(len(o), dtype=RADIANCE_DTYPE)
+        opts = path_opts(max_bounce, environmental_light)
+        _check(lib().rt2_radiance_rays_host(self._p, rays.ctypes.data, len(rays), C.byref(opts), state.ctypes.data,
+                                            out.ctypes.data, int(flags)), "rt2_radiance_rays_host")
+        return out, state
+
+    def radiance_device(self, rays_ptr: int, n: int, rng_ptr: int, out_ptr: int, max_bounce: int = 8,
+                        environmental_light: bool = True, flags: int = 0, stream: int = 0) -> None:
+        """Asynchronous radiance query over device arrays of n rt2_ray records, uint32 stream states (read and
+        written) and rt2_radiance records (rt2_radiance_rays)."""
+        opts = path_opts(max_bounce, environmental_light)
+        _check(lib().rt2_radiance_rays(self._p, C.c_void_p(rays_ptr) if rays_ptr else None, int(n), C.byref(opts),
+                                       C.c_void_p(rng_ptr) if rng_ptr else None,
+                                       C.c_void_p(out_ptr) if out_ptr else None, int(flags),
+                                       C.c_void_p(stream) if stream else None), "rt2_radiance_rays")
+
+    def path_rays(self, u: Uniforms, frame_index: int, sh: Optional[Shard] = None, rng=None):
+        """The path tracer's jittered camera rays of the slab's pixels
+        (rt2_path_rays_host, blocking).  rng=None seeds every pixel's stream
+        for `frame_index` as the render does; otherwise rng (one uint32 per
+        slab pixel) is the streams' states, used as found.  Returns (rays,
+        rng): a RAY_DTYPE array in slab-row order and the states after the
+        three draws of each ray.  The caller's rng array is not modified."""
+        sh = sh or shard()
+        rows = shard_rows(u.height, sh)
+        if rows < 0:
+            raise RT2Error("path_rays: bad shard")
+        n = rows * int(u.width)
+        rays = np.zeros(n, dtype=RAY_DTYPE)
+        if rng is None:
+            state = np.zeros(n, dtype=np.uint32)
+        else:
+            state = np.array(rng, dtype=np.uint32).reshape(-1)
+            if len(state) != n:
+                raise RT2Error(f"path_rays: {len(state)} rng states for {n} pixels")
+        _check(lib().rt2_path_rays_host(self._p, C.byref(u), sh, int(frame_index) & 0xFFFFFFFF, int(rng is None),
+                                        state.ctypes.data if n else None, rays.ctypes.data if n else None),
+               "rt2_path_rays_host")
+        return rays, state
+
+    def path_rays_device(self, u: Uniforms, frame_index: int, sh: Shard, reseed: bool, rng_ptr: int, rays_ptr: int,
+                         stream: int = 0) -> None:
+        """Asynchronous: the slab's path-tracer camera rays into a device array of rt2_ray records, the streams'
+        states in a device array of uint32 (rt2_path_rays)."""
+        _check(lib().rt2_path_rays(self._p, C.byref(u), sh, int(frame_index) & 0xFFFFFFFF, int(bool(reseed)),
+                                   C.c_void_p(rng_ptr) if rng_ptr else None,
+                                   C.c_void_p(rays_ptr) if rays_ptr else None,
+                                   C.c_void_p(stream) if stream else None), "rt2_path_rays")
+
+    def radiance_image(self, u: Uniforms, frame_index: int, sh: Optional[Shard] = None, flags: int = 0):
+        """The linear (HDR) image of one frame of a view: the mean over
+        u.numRaysPerPixel samples of trace(), before the tonemap and the sRGB
+        encoding that render_host applies.  path_rays_device and
+        radiance_device are chained on one stream over device buffers, one
+        random stream per pixel seeded for `frame_index`; the samples are added
+        in order on the device and divided by numRaysPerPixel in binary32 on
+        the host.  Returns ((rows, W, 3) float32, (rows, W) int64 segment
+        counts).  u.numTextures is not consulted: a ray query takes the number
+        of images given to set_textures."""
+        import torch
+
+        sh = sh or shard()
+        rows = shard_rows(u.height, sh)
+        if rows < 0:
+            raise RT2Error("radiance_image: bad shard")
+        W, R = int(u.width), int(u.numRaysPerPixel)
+        n = rows * W
+        total = np.zeros((n, 3), dtype=np.float32)
+        segs = np.zeros(n, dtype=np.int64)
+        if n and R > 0:
+            dev = torch.device("cuda", self.device)
+            with torch.cuda.device(dev):
+                rays = torch.empty(n * RAY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                rng = torch.empty(n, dtype=torch.int32, device=dev)
+                out = torch.empty(n * RADIANCE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                acc = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+                cnt = torch.zeros(n, dtype=torch.int64, device=dev)
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                for k in range(R):
+                    self.path_rays_device(u, frame_index, sh, k == 0, rng.data_ptr(), rays.data_ptr(), stream)
+                    self.radiance_device(rays.data_ptr(), n, rng.data_ptr(), out.data_ptr(), int(u.maxBounceCount),
+                                         bool(u.environmentalLight), flags, stream)
+                    acc += out.view(torch.float32).view(n, 4)[:, :3]
+                    cnt += out.view(torch.int32).view(n, 4)[:, 3]
+                total = acc.cpu().numpy()  # the copy waits for the stream
+                segs = cnt.cpu().numpy()
+        img = total / np.float32(max(R, 1))
+        return img.reshape(rows, W, 3), segs.reshape(rows, W)
+
     def last_kernel(self) -> int:
         """What the scene launched last (rt2_scene_diag): a render's variant id (-1: the traceBasic preview), or
         after a query QUERY_RES (trace_rays_k5r, every group resident), QUERY_RES_L2 (its L2 continuation),
         QUERY_SCALAR or QUERY_BVH (trace_rays_scalar); after an occlusion query OCCLUDED_RES, OCCLUDED_RES_L2
         (occluded_k5r), OCCLUDED_SCALAR or OCCLUDED_BVH (occluded_scalar); after a surface query SURFACE_RES,
         SURFACE_RES_L2 (surface_k5r), SURFACE_SCALAR or SURFACE_BVH (surface_scalar); after a preview shading query
-        SHADE_RES, SHADE_RES_L2 (shade_rays_k5r), SHADE_SCALAR or SHADE_BVH (shade_rays_scalar)."""
+        SHADE_RES, SHADE_RES_L2 (shade_rays_k5r), SHADE_SCALAR or SHADE_BVH (shade_rays_scalar); after a radiance
+        query RADIANCE_RES, RADIANCE_RES_L2 (radiance_rays_k5r), RADIANCE_SCALAR or RADIANCE_BVH
+        (radiance_rays_scalar)."""
         c, v = (C.c_ulonglong * 8)(), C.c_int(-1)
         if lib().rt2_scene_diag(self._p, c, C.byref(v)) != 0:
             raise RT2Error("rt2_scene_diag failed")
