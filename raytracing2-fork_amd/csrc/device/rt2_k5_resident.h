@@ -90,6 +90,12 @@
 // Every term is the sum of the same 16 f16 products as in the 32-row form (the
 // other 16 k-slots add zeros), so the filter's guarantee is unchanged.
 //
+// MfmaSpec::cluster_rows8 (353, 354): a compact cluster that at most 8 live
+// rays need is swept with one 16-row fragment that holds each ray twice, as
+// [ray | 0] in rows 0..7 and as [0 | ray] in rows 8..15, so three products per
+// group give both triangle halves (cluster_rows_frag8; rt2_mfma.h kt_group8;
+// DESIGN.md "8-row products").  The terms are those of the 16-row form.
+//
 // MfmaSpec::slot_order (353, 354): the scene's triangles are regrouped by
 // place at upload (rt2_cluster_order_build) and the sweep reads that slot
 // image: records, table and the episode's triangles in slot order.  A ray's
@@ -405,6 +411,10 @@ struct ClusterDiag {
     unsigned long long skipped = 0, one = 0, two = 0, rays = 0;
     unsigned long long r16 = 0;  // ... of `one`, the cases at most 16 rays need (MfmaSpec::cluster_rows16's form)
 };
+// ... with MfmaSpec::cluster_rows8 (a type of its own: 411's and 416's code stays as it was)
+struct ClusterDiag8 : ClusterDiag {
+    unsigned long long r8 = 0;  // ... of `one`, the cases at most 8 rays need (MfmaSpec::cluster_rows8's form)
+};
 
 // MfmaSpec::cluster_rows.  One 32-row fragment out of a0[0] / a0[1] that holds
 // the rays of `need` (at most 32 of them) in its rows 0 .. c - 1; the other
@@ -473,6 +483,41 @@ __device__ __forceinline__ void cluster_rows_frag16(const h8* a0, unsigned long 
     }
     alo = __builtin_bit_cast(h8, rl);
     ahi = __builtin_bit_cast(h8, rh);
+}
+
+// MfmaSpec::cluster_rows8.  kt_group8's fragment for the rays of `need` (at
+// most 8 of them): cluster_rows_frag16's ranking and permutes, whose selected
+// register q holds row r < 16's two k-quarters in lanes r and r + 16.  Rows
+// 0..7 stay there; one v_permlane32_swap into zero and a row shift by 8 copy
+// them to lanes r + 40 and r + 56; every other lane is zero:
+// a8[l] = l < 32 ? ((l & 15) < 8 ? q[l] : 0) : ((l & 15) >= 8 ? q[l - 40] : 0).
+// Rows c .. 7 hold other rays of the wave, as rows c .. 15 do there.  No LDS.
+__device__ __forceinline__ h8 cluster_rows_frag8(const h8* a0, unsigned long long need) {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const int l = (int)lane_id();
+    const int c0 = __popc((uint32_t)need), c1 = __popc((uint32_t)(need >> 32));
+    const int rk = (int)lanes_below(need);
+    const bool nb = (need >> l) & 1ull;
+    const int rest = ((l - rk) + (l < 32 ? c0 : c1 + 2 * c0)) & 31;
+    const uint32_t row = (uint32_t)(nb ? rk : rest);
+    const uint32_t dst = row + (row & 16);
+    const auto sw = __builtin_amdgcn_permlane32_swap(dst, dst, false, false);
+    const int half = (l & 32) >> 1;
+    const int to0 = 4 * ((int)sw[0] + half), to1 = 4 * ((int)sw[1] + half);
+    const u4 b0 = __builtin_bit_cast(u4, a0[0]), b1 = __builtin_bit_cast(u4, a0[1]);
+    const bool first = (l & 15) < c0, keep = (l & 0x28) == 0;  // l < 32 and (l & 15) < 8
+    u4 r;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int x0 = __builtin_amdgcn_ds_permute(to0, (int)b0[k]);
+        const int x1 = __builtin_amdgcn_ds_permute(to1, (int)b1[k]);
+        const uint32_t q = (uint32_t)(first ? x0 : x1);
+        const uint32_t up = __builtin_amdgcn_permlane32_swap(0u, q, false, false)[0];  // [0 | q's lanes 0..31]
+        // row_shr:8, out-of-row lanes 0: lanes 40..47 and 56..63 take q[0..7] and q[16..23], every other lane 0
+        const uint32_t sh = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)up, 0x118, 0xf, 0xf, true);
+        r[k] = keep ? q : sh;
+    }
+    return __builtin_bit_cast(h8, r);
 }
 
 // MfmaSpec::slot_order.  The slot image of a resident scene, one allocation
@@ -679,6 +724,28 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
                             }
                             tb = t - d16;
                         };
+                        // MfmaSpec::cluster_rows8: groups [j, j1) in the 8-row form with fragment a8, two per
+                        // trip; the records as in the 16-row form
+                        [[maybe_unused]] auto one_block8 = [&](const h8& a8, int j, int j1) {
+                            const int d16 = kt16_record_lane(lane) - lane;
+                            const h8* t = tb + d16;
+                            for (; j + 1 < j1; j += 2) {
+                                uint32_t m0, m1;
+                                kt_group8_2(a8, t[0], t[64], t[128], t[kKtOps * 64], t[kKtOps * 64 + 64],
+                                            t[kKtOps * 64 + 128], m0, m1);
+                                maskv = rt2_writelane((int)m0, j, maskv);
+                                maskv = rt2_writelane((int)m1, j + 1, maskv);
+                                any |= m0 | m1;
+                                t += 2 * kKtOps * 64;
+                            }
+                            if (j < j1) {
+                                const uint32_t m32 = kt_group8(a8, t[0], t[64], t[128]);
+                                maskv = rt2_writelane((int)m32, j, maskv);
+                                any |= m32;
+                                t += kKtOps * 64;
+                            }
+                            tb = t - d16;
+                        };
 #pragma nounroll
                         for (int k = 0; k < ncl; k++) {
                             const int g0 = __float_as_int(ct[8 * k + 3]), gf = __float_as_int(ct[8 * k + 7]);
@@ -698,10 +765,19 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
                                     else
                                         cd->two += 1;
                                     if (c && c <= 16) cd->r16 += 1;
+                                    if constexpr (S.cluster_rows8)
+                                        if (c && c <= 8) static_cast<ClusterDiag8*>(cd)->r8 += 1;
                                 }
                             if (!c) {  // no live ray can meet the box: the groups' hot masks stay 0
                                 tb += (g1 - g0) * (kKtOps * 64);
                                 continue;
+                            }
+                            if constexpr (S.cluster_rows8) {
+                                static_assert(S.cluster_rows16, "cluster_rows8: the 16-row form takes 9 to 16 rays");
+                                if (compact && c <= 8) {  // whether or not `upper`, as below
+                                    one_block8(cluster_rows_frag8(a0, need), g0, g1);
+                                    continue;
+                                }
                             }
                             if constexpr (S.cluster_rows16)
                                 if (compact && c <= 16) {
@@ -863,7 +939,8 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
     lane_init(L);
     MfmaDiag dg;
     struct NoClusterDiag {};
-    [[maybe_unused]] std::conditional_t<S.cluster_rows, ClusterDiag, NoClusterDiag> cdg;
+    [[maybe_unused]] std::conditional_t<S.cluster_rows8, ClusterDiag8,
+                                        std::conditional_t<S.cluster_rows, ClusterDiag, NoClusterDiag>> cdg;
     [[maybe_unused]] PathDiagSlot<S.diag> pds;
     const int wave = (int)(threadIdx.x >> 6);
     // MfmaSpec::lean: the wave counts its lanes' segments (no per-lane counter)
@@ -1059,6 +1136,8 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
                 atomicAdd(p.seg_counter + 26, cdg.two);      // ... more than 32 rays need it: two blocks
                 atomicAdd(p.seg_counter + 27, cdg.rays);     // ... the rays that need it, summed
                 atomicAdd(p.seg_counter + 28, cdg.r16);      // ... at most 16 rays need it (and at least one)
+                // (slot 29 is the scene's scratch word for the record preparation's flags)
+                if constexpr (S.cluster_rows8) atomicAdd(p.seg_counter + 30, cdg.r8);  // ... at most 8 (and at least one)
             }
         }
 }

@@ -80,6 +80,10 @@ struct MfmaSpec {
     bool cluster_rows16 = false;  // with cluster_rows: a compact cluster that at most 16 rays need is swept with 16-row
                                   // products (v_mfma_f32_16x16x32_f16: 4 accumulator registers instead of 16), six per
                                   // group for the triangles' two halves (kt_group16; DESIGN.md "16-row products")
+    bool cluster_rows8 = false;  // with cluster_rows16: a compact cluster that at most 8 rays need is swept with one
+                                 // 16-row fragment that holds each ray twice, [ray | 0] in rows 0..7 and [0 | ray] in
+                                 // rows 8..15: three products per group give both triangle halves (kt_group8;
+                                 // DESIGN.md "8-row products")
     bool slot_order = false;  // with cluster_rows and exact_lanes: RenderParams::mfma_kt_frag is the scene's slot image
                               // (records, table, triangles and slot_tri of the triangles in slot order); the episode
                               // breaks distance ties by the triangles' indices and the sweep returns an index
@@ -763,6 +767,49 @@ __device__ __forceinline__ void kt_group16_2(const h8& alo, const h8& ahi, const
     m1 = kt16_hot(__ballot(al1 < 0), __ballot(ah1 < 0));
 }
 
+// MfmaSpec::cluster_rows8.  The filter of 8 rays by one 16-row product per
+// quantity: fragment a8 holds ray r < 8 twice, [ray | 0] in row r (lanes r,
+// r + 16) and [0 | ray] in row r + 8 (lanes r + 40, r + 56), every other lane
+// zero.  Against the record register of kt_group16, D row r is (ray r,
+// triangle j) and D row r + 8 is (ray r, triangle j + 16): each term the sum of
+// the same 16 f16 products as alo's and ahi's, the other 16 slots adding
+// 0 x finite.  Lanes 0..31 of D hold rows 0..7 and lanes 32..63 rows 8..15, so
+// one ballot has triangle j in bits j and j + 16 and triangle j + 16 in bits
+// j + 32 and j + 48.  3 products, 4 ANDs, 2 ORs and one compare per group.
+__device__ __forceinline__ uint32_t kt8_hot(unsigned long long M) {
+    const uint32_t lo = (uint32_t)M, hi = (uint32_t)(M >> 32);
+    return ((lo | lo >> 16) & 0xffffu) | (hi | hi >> 16) << 16;
+}
+// one group: its hot mask
+__device__ __forceinline__ uint32_t kt_group8(const h8& a8, const h8& bu, const h8& bv, const h8& bx) {
+    const f4v zero = {};
+    const f4v U = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, bu, zero, 0, 0, 0);
+    const f4v V = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, bv, zero, 0, 0, 0);
+    const f4v X = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, bx, zero, 0, 0, 0);
+    const int a = kt16_fold(U, V, X);
+    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);  // MFMA
+    __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);  // VALU
+    return kt8_hot(__ballot(a < 0));
+}
+// two groups per trip, the second group's products beside the first one's
+// fold: [g0] [g1] [fold g0] [fold g1]; 24 product registers live
+__device__ __forceinline__ void kt_group8_2(const h8& a8, const h8& bu0, const h8& bv0, const h8& bx0, const h8& bu1,
+                                            const h8& bv1, const h8& bx1, uint32_t& m0, uint32_t& m1) {
+    const f4v zero = {};
+    const f4v U0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, bu0, zero, 0, 0, 0);
+    const f4v V0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, bv0, zero, 0, 0, 0);
+    const f4v X0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, bx0, zero, 0, 0, 0);
+    const f4v U1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, bu1, zero, 0, 0, 0);
+    const f4v V1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, bv1, zero, 0, 0, 0);
+    const f4v X1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, bx1, zero, 0, 0, 0);
+    const int a0 = kt16_fold(U0, V0, X0);
+    const int a1 = kt16_fold(U1, V1, X1);
+    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);   // MFMA
+    __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);  // VALU
+    m0 = kt8_hot(__ballot(a0 < 0));
+    m1 = kt8_hot(__ballot(a1 < 0));
+}
+
 // Closest hit of every lane's ray (o, d) over all triangles, records read
 // from L2; the whole wave calls it (lanes without a ray of their own carry a
 // copy of a live one).  Five products per 32-ray block: U, -V, X from the
@@ -1095,7 +1142,8 @@ __device__ __forceinline__ K16Terms k16_terms(const h8& a0, const h8& a1, const 
 // 8-product k16 form, 2 = the 5-product form, 3 = the 5-product form with the
 // threshold in the accumulator, 4 = layout 3 on frag_pair fragments, 5 = the
 // threshold in the K-slots, 6 = layout 5 with each ray's own W, 7 = layout 6's
-// U, -V, X by the 16-row products (MfmaSpec::cluster_rows16).
+// U, -V, X by the 16-row products (MfmaSpec::cluster_rows16), 8 = the same by
+// the 8-row products (MfmaSpec::cluster_rows8).
 template <int LAYOUT>
 __global__ __launch_bounds__(64) void mfma_probe_kernel(RenderParams p, const float4* rays, int n_pad, float* terms,
                                                         _Float16* frags, float* rinfo, uint8_t* accept) {
@@ -1203,6 +1251,42 @@ __global__ __launch_bounds__(64) void mfma_probe_kernel(RenderParams p, const fl
                             tt[1] = q[h][1][i];
                             tt[2] = q[h][2][i];
                         }
+                }
+            }
+            return;
+        }
+        if constexpr (LAYOUT == 8) {
+            // MfmaSpec::cluster_rows8: U, -V, X of layout 6 by kt_group8's
+            // products.  Each 8 rays of the wave in turn are rows 0..7 as
+            // [ray | 0] and rows 8..15 as [0 | the same ray], every other lane
+            // of the fragment zero; the records through kt16_record_lane.
+            typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+            const h8* fg16 = reinterpret_cast<const h8*>(p.mfma_kt_frag) + kt16_record_lane(lane);
+            const f4v zero4 = {};
+            const bool holds = lane < 32 ? (lane & 15) < 8 : (lane & 15) >= 8;
+            for (int R8 = 0; R8 < 8; R8++) {
+                const u4 src = __builtin_bit_cast(u4, a0[R8 >> 2]);
+                u4 f;
+                for (int k = 0; k < 4; k++) {
+                    const uint32_t v = (uint32_t)__shfl((int)src[k], 8 * (R8 & 3) + (lane & 7) + 32 * ((lane >> 4) & 1));
+                    f[k] = holds ? v : 0u;
+                }
+                const h8 a8 = __builtin_bit_cast(h8, f);
+                for (int G = 0; G < n_pad / 32; G++) {
+                    const h8* t = fg16 + (size_t)G * kKtOps * 64;
+                    f4v q[3];
+                    for (int op = 0; op < 3; op++)
+                        q[op] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, t[64 * op], zero4, 0, 0, 0);
+                    // D rows 4 (lane >> 4) + i: rows 0..7 are the rays against triangles 0..15, rows 8..15 the
+                    // same rays against triangles 16..31
+                    for (int i = 0; i < 4; i++) {
+                        const int row = 4 * (lane >> 4) + i;
+                        const size_t rr = ray0 + 8 * R8 + (row & 7);
+                        float* tt = terms + (rr * n_pad + 32 * G + 16 * (row >> 3) + (lane & 15)) * 5;
+                        tt[0] = q[0][i];
+                        tt[1] = q[1][i];
+                        tt[2] = q[2][i];
+                    }
                 }
             }
             return;

@@ -713,6 +713,12 @@ constexpr MfmaSpec kt_cr16(MfmaSpec x) {
     x.cluster_rows16 = true;
     return x;
 }
+// ... and a compact cluster that at most 8 rays need with 8-row products (MfmaSpec::cluster_rows8; DESIGN.md "8-row
+// products")
+constexpr MfmaSpec kt_cr8(MfmaSpec x) {
+    x.cluster_rows8 = true;
+    return x;
+}
 // ... on the scene's slot image: triangles regrouped by place, groups swept in slot order (MfmaSpec::slot_order;
 // DESIGN.md "Slot order")
 constexpr MfmaSpec kt_slot(MfmaSpec x) {
@@ -765,9 +771,10 @@ constexpr Variant kVariants[] = {
     // (DESIGN.md "Exact tests per ray"), two groups per trip of the products' loop with the hot masks by v_writelane
     // (DESIGN.md "Two groups per loop trip") and keep each pixel's camera end point in LDS instead of recomputing it
     // per ray (DESIGN.md "The camera end point once per pixel")
-    // and sweep the scene's slot image (DESIGN.md "Slot order")
-    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_slot(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups, true),
-    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_slot(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups, true),
+    // and sweep the scene's slot image (DESIGN.md "Slot order"), a compact cluster that at most 8 rays need with 8-row
+    // products (DESIGN.md "8-row products")
+    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups, true),
+    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin)))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups, true),
     RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, true, 4), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
     RT2_VARIANT(356, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, true, true), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw", kResL2Groups),
     // the default above 8,192 triangles: the LDS-tiled kernel (rt2_k5_tiles.h; 19-group tiles, fragments in
@@ -832,6 +839,11 @@ constexpr Variant kVariants[] = {
     RT2_VARIANT(414, K_MFMA, render_mfma_k5r<kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/idx", kResGroups),
     RT2_VARIANT(415, K_MFMA, render_mfma_k5r<kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/idx", kResGroups),
     RT2_VARIANT(416, K_MFMA, render_mfma_k5r<kt_slot(kt_cr16(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 0, true), kResWin)))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/xl/cr16/slot", kResGroups, true),
+    // the 8-row products for clusters that at most 8 rays need (MfmaSpec::cluster_rows8; 353 / 354 take it): 353's and
+    // 354's specs with the 16-row products alone (r16: the form before), and 416's counters with the 8-row count
+    RT2_VARIANT(417, K_MFMA, render_mfma_k5r<kt_slot(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/r16", kResGroups, true),
+    RT2_VARIANT(418, K_MFMA, render_mfma_k5r<kt_slot(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/r16", kResGroups, true),
+    RT2_VARIANT(419, K_MFMA, render_mfma_k5r<kt_slot(kt_cr8(kt_cr16(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 0, true), kResWin))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/xl/cr8/slot", kResGroups, true),
     // the tile stream at 3 waves per SIMD (380 takes 4 with the lean lane state): with its diagnostic clocks; without
     // flow_prio; with the lean lane state
     RT2_VARIANT(370, K_MFMA, render_mfma_k5t<kt_tiles_flow()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp"),
@@ -2356,7 +2368,8 @@ extern "C" int rt2_scene_set_slot_order(rt2_scene* s, const int32_t* slot_tri, c
 // 5 = the threshold in the K-slots (render_mfma_k5r / render_mfma_k5t,
 // frag_pair fragments: U, -V, X, Y, slot 3 zero), 6 = layout 5 with each
 // ray's own W (MfmaSpec::kt_lane_w), 7 = layout 6's U, -V, X by the 16-row
-// products of MfmaSpec::cluster_rows16 (kt_group16's operands; terms 3, 4 stay 0).
+// products of MfmaSpec::cluster_rows16 (kt_group16's operands; terms 3, 4 stay 0),
+// 8 = the same by the 8-row products of MfmaSpec::cluster_rows8 (kt_group8's operands).
 // Host outputs, sized by the caller: terms [n_rays][n_pad][5]
 // (n_pad = triangles padded to 16 / 32), frags [n_rays][80] f16 bits (the LDS
 // row of layouts 0..3: main slots 0..31 and Y slots 16..31; layouts 4, 5 also
@@ -2365,7 +2378,7 @@ extern "C" int rt2_scene_set_slot_order(rt2_scene* s, const int32_t* slot_tri, c
 extern "C" int rt2_mfma_probe(rt2_scene* s, int layout, const float* rays, int32_t n_rays, float* terms,
                               uint16_t* frags, float* rinfo, uint8_t* accept) {
     if (!s || !rays || n_rays <= 0 || n_rays % 64 != 0 || !terms || !frags || !rinfo || !accept ||
-        layout < 0 || layout > 7 || s->n_tris < 1 || !s->mfma_ok) {
+        layout < 0 || layout > 8 || s->n_tris < 1 || !s->mfma_ok) {
         rt2h::set_error("rt2_mfma_probe: bad argument (n_rays a positive multiple of 64, a scene in the filter's "
                         "range)");
         return -1;
@@ -2411,7 +2424,8 @@ extern "C" int rt2_mfma_probe(rt2_scene* s, int layout, const float* rays, int32
         case 4: launch(mfma_probe_kernel<4>); break;
         case 5: launch(mfma_probe_kernel<5>); break;
         case 6: launch(mfma_probe_kernel<6>); break;
-        default: launch(mfma_probe_kernel<7>); break;
+        case 7: launch(mfma_probe_kernel<7>); break;
+        default: launch(mfma_probe_kernel<8>); break;
         }
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipDeviceSynchronize());

@@ -58,13 +58,15 @@ double compact_cost(int n, double r) {
 }
 
 // The prices of the slot-order rule (DESIGN.md "Slot order": the listings of
-// "Compact clusters" and "16-row products"), per wave and sweep.  A compact
-// cluster of n groups pays its need test and loop share, then by the number c
-// of rays that need it: nothing (c = 0), the 16-row products (c <= 16) where
-// they are cheaper, the one-block form (c <= 32), the two-block form.
+// "Compact clusters", "16-row products" and "8-row products"), per wave and
+// sweep.  A compact cluster of n groups pays its need test and loop share,
+// then by the number c of rays that need it: nothing (c = 0), the 8-row
+// products (c <= 8) and the 16-row products (c <= 16) where they are cheaper,
+// the one-block form (c <= 32), the two-block form.
 constexpr double kSlotCompact = 31.0, kSlotFull = 8.0, kSlotGroup = 51.5;
 double price32(int n) { return 28.0 + 53.0 * (n / 2) + 27.0 * (n % 2); }
 double price16(int n) { return std::min(38.0 + 31.0 * (n / 2) + 16.0 * (n % 2), price32(n)); }
+double price8(int n) { return std::min(45.0 + 17.0 * (n / 2) + 9.0 * (n % 2), price16(n)); }
 // c is taken as binomial over a wave's 64 rays that each need the cluster
 // with probability r, the area share of compact_cost above.  Dead lanes only
 // lower c, which makes a compact cluster cheaper and never dearer.
@@ -75,7 +77,7 @@ double slot_compact_cost(int n, double r) {
     double pm = std::pow(1.0 - r, kSlotRays), e = 0.0;  // pm = P(c = 0): the skip term
     for (int c = 1; c <= kSlotRays; c++) {
         pm *= (double)(kSlotRays - c + 1) / c * (r / (1.0 - r));
-        e += pm * (c <= 16 ? price16(n) : c <= 32 ? price32(n) : kSlotGroup * n);
+        e += pm * (c <= 8 ? price8(n) : c <= 16 ? price16(n) : c <= 32 ? price32(n) : kSlotGroup * n);
     }
     return kSlotCompact + e;
 }

@@ -1011,7 +1011,8 @@ class Scene:
         accumulator (cthr: U, -V, X, Y shifted by TT, TT in slot 3), 4 = layout 3 with the fragments built in
         registers (frag_pair: the operand path of the shipping kernels), 5 = the threshold in the K-slots (kthr:
         U, -V, X, Y; slot 3 zero; frag_pair fragments), 6 = layout 5 with each ray's own W, 7 = layout 6's U, -V, X
-        by the 16-row products of MfmaSpec::cluster_rows16 (slots 3, 4 zero).  Returns (terms [n, n_pad, 5], frags [n, 48] float16
+        by the 16-row products of MfmaSpec::cluster_rows16 (slots 3, 4 zero), 8 = the same by the 8-row products of
+        MfmaSpec::cluster_rows8.  Returns (terms [n, n_pad, 5], frags [n, 48] float16
         (layouts 4, 5: [n, 80], the register fragments at 48..63 and 64..79), rinfo [n, 8], accept [n, n_tris]
         bool)."""
         rays = np.ascontiguousarray(rays, dtype=np.float32)

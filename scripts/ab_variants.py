@@ -89,9 +89,11 @@ for rnd in range(a.rounds):
                                                needing_rays_per_case=round(c[28] / cases, 2),
                                                # ... of one_block, at most 16 rays need it (MfmaSpec::cluster_rows16)
                                                rows16=round(c[29] / cases, 4),
+                                               # ... at most 8 (MfmaSpec::cluster_rows8; counted by 419 alone)
+                                               rows8=round(c[31] / cases, 4),
                                                counts=dict(skipped=int(c[25]), one_block=int(c[26]),
                                                            two_blocks=int(c[27]), needing_rays=int(c[28]),
-                                                           rows16=int(c[29])))
+                                                           rows16=int(c[29]), rows8=int(c[31])))
             tf = [c[13], c[14], c[15], c[16], c[17]]  # render_mfma_k5t tile_flow diag: wait, filter, exact, sweep, life
             if tf[4]:
                 diag[v]["flow_clock_share"] = dict(

@@ -82,6 +82,15 @@ for v in [int(x) for x in a.variants.split(",")]:
                                    rnd_dir_trips_per_wave_segment=round(rd_trips / max(sweeps, 1), 3),
                                    new_ray_blocks_per_wave_segment=round(new_ray / max(sweeps, 1), 4),
                                    new_frame_blocks_per_wave_segment=round(new_px / max(sweeps, 1), 4)))
+        # ClusterDiag (MfmaSpec::cluster_rows diag: 411, 416, 419): the (wave, compact cluster) cases of the sweeps;
+        # rows8 (the cases of 1 to 8 needing rays) is counted by 419 alone
+        cases = c[25] + c[26] + c[27]
+        if cases:
+            res[name_of(v)].update(
+                cluster_rows=dict(skipped=int(c[25]), one_block=int(c[26]), two_blocks=int(c[27]),
+                                  needing_rays=int(c[28]), rows16=int(c[29]), rows8=int(c[31]),
+                                  needing_rays_per_case=round(c[28] / cases, 2),
+                                  rows16_share=round(c[29] / cases, 4), rows8_share=round(c[31] / cases, 4)))
         # MfmaDiag::xl: per episode, the (ray, triangle) pairs that pass the filter's U, -V, X conditions, the
         # largest count of one ray (what a per-lane test loop runs; exact_lanes arms: its iterations) and the
         # rounds of 32 hot triangles
