@@ -489,6 +489,68 @@ int rt2_path_rays_host(rt2_scene* scene, const rt2_uniforms* uniforms, rt2_shard
                        int reseed, uint32_t* rng, rt2_ray* rays);
 
 /* ------------------------------------------------------------------------
+ * (1a-6) Linear renders: rt2_render's paths, HDR sums and second moments
+ *
+ * rt2_render_linear is rt2_render with another sink: the same pixels, frames,
+ * seeds, draws and trace() calls on the same kernels' schedule, but what it
+ * accumulates is the frame's linear mean, before aces1 and srgb1, and
+ * (optionally) the mean of the samples' squares.  For every pixel p of the
+ * shard's slab (slab-row order, as rt2_render) and every frame f = frame_begin
+ * + i, in increasing i:
+ *   - seed = x + y * width + f * 968824447u, and for sample s = 0 .. R-1 (R =
+ *     numRaysPerPixel) the jittered ray and v_s = trace(ray, seed) exactly as
+ *     in rt2_render: the same draws in the same order;
+ *   - from c = q = (0,0,0), per channel and in sample order, c = c + v_s and
+ *     q = q + v_s * v_s: the product is rounded to binary32, then the sum (no
+ *     fused multiply-add);
+ *   - m = c / (float)R and m2 = q / (float)R (IEEE division, the render's own);
+ *   - d_sum[4*p + ch] += m[ch] and, when d_sumsq is not NULL,
+ *     d_sumsq[4*p + ch] += m2[ch] (ch = 0, 1, 2); the fourth float of both
+ *     records is written 0.0f, as rt2_render writes its accumulator's.
+ * Frames are added in increasing order, so splitting them over several calls
+ * gives identical bits; rt2_scene_set_frame_split, _set_cost_order,
+ * _set_variant and _set_traversal change nothing in the result.
+ * d_sum and d_sumsq are DEVICE memory of rows * width * 4 floats, aligned to
+ * 16 bytes.  The call is asynchronous on `stream` and ordered against the
+ * scene's other launches as renders are.  rt2_scene_stats counts it exactly as
+ * it counts rt2_render (samples, segments, tests, node_visits);
+ * uniforms->numTextures is used as rt2_render uses it; maxBounceCount <= 0
+ * adds sums of 0, as the render's trace() returns 0.
+ * The kernel is the linear twin of the variant rt2_render would launch for the
+ * same call (the same selection, the same rt2_scene_set_variant rules applied
+ * to the id the caller set): rt2_scene_diag reports the variant's id + 1000
+ * (1136 for the automatic 0) and rt2_variant_name gives the parent's name with
+ * "/lin" appended.  A forced variant without a twin (experiment builds) falls
+ * back to the automatic choice.  A twin's id is not accepted by
+ * rt2_scene_set_variant.
+ * Bad arguments return < 0 before any device call: a null scene, uniforms or
+ * d_sum; d_sum or d_sumsq not aligned to 16 bytes; numRaysPerPixel < 1; zero
+ * width or height; a bad shard; basicShading != 0 (the preview has no
+ * tonemap: rt2_render already gives its linear value).  frame_count == 0 or
+ * an empty slab returns 0 and launches nothing.
+ *
+ * rt2_render_linear_host is the blocking form, like rt2_render_host: it
+ * renders into device buffers the scene keeps (freed by rt2_scene_destroy) on
+ * the scene's own stream and returns out_mean[4*p + ch] = sum / frames and,
+ * when out_meansq is not NULL, out_meansq[4*p + ch] = sumsq / frames
+ * (rt2_resolve_rgba32f's division, alpha = 1, slab-row order; host arrays of
+ * rows * width * 4 floats, no alignment requirement).
+ *
+ * rt2_resolve_tonemap is the device resolve from a linear sum to the render's
+ * display value: out[4*i + ch] = srgb1(aces1(d_linear_sum[4*i + ch] / frames))
+ * with the render's pinned aces1 and srgb1, alpha = 1.  For a one-frame linear
+ * sum (frames = 1) this is bit for bit the pixel rt2_render adds to its
+ * accumulator for that frame.  Asynchronous; in place (d_out == d_linear_sum)
+ * is allowed.  Bad arguments as rt2_resolve_rgba32f (a null pointer,
+ * n_pixels < 0, frames == 0).
+ * ---------------------------------------------------------------------- */
+int rt2_render_linear(rt2_scene* scene, const rt2_uniforms* uniforms, uint32_t frame_begin, uint32_t frame_count,
+                      rt2_shard shard, float* d_sum, float* d_sumsq, void* stream);
+int rt2_render_linear_host(rt2_scene* scene, const rt2_uniforms* uniforms, uint32_t frame_begin,
+                           uint32_t frame_count, rt2_shard shard, float* out_mean, float* out_meansq);
+int rt2_resolve_tonemap(const float* d_linear_sum, int64_t n_pixels, uint32_t frames, float* d_out, void* stream);
+
+/* ------------------------------------------------------------------------
  * (1b) Multi-GPU: row-tile shards + one RCCL gather
  *
  * The reference renders on one GPU and reads the framebuffer back with

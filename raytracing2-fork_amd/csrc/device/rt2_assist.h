@@ -36,6 +36,7 @@ struct AssistSpec {
     Filter filter;
     int waves;       // minimum waves per SIMD the register allocation must allow
     int coop_rays;   // with helpers: ray jobs for at most this many live rays (chunk jobs above)
+    bool linear = false;  // the linear sink (rt2_render_linear; rt2_path.h end_path_linear)
 };
 
 template <int NW>
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(64 * S.waves_per_block) __attribute__((amdgpu_waves
     if (p.wave_log) t_start = __builtin_amdgcn_s_memrealtime();
     if (w < cap) {
         for (;;) {
-            advance(L, p);
+            advance<1, true, false, false, S.linear>(L, p);
             const unsigned long long act = __ballot(L.st == ST_TRACE);
             if (p.wave_log && !t_dry && __any(L.st == ST_DONE)) t_dry = __builtin_amdgcn_s_memrealtime();
             if (!act) break;
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(64 * S.waves_per_block) __attribute__((amdgpu_waves
             if (L.st == ST_TRACE) {
                 L.bounce += 1;
                 L.segs += 1;
-                shade(L, p, best, bi);
+                shade<1, false, S.linear>(L, p, best, bi);
             }
         }
         if (lane == 0) __hip_atomic_fetch_add(&sh.busy, -1, __ATOMIC_RELAXED, WG);

@@ -23,6 +23,7 @@ struct SmemSpec {
     int waves;       // minimum waves per SIMD the register allocation must allow (1 = unconstrained)
     bool stats;      // diagnostic build: filter survivor counters
     bool lockstep = false;  // one workgroup barrier per segment: the waves start their sweeps together
+    bool linear = false;  // the linear sink (rt2_render_linear; rt2_path.h end_path_linear)
 };
 struct SplitSpec {
     int waves_per_ray;  // S: waves that trace the same 64 rays (1/S of the triangles each)
@@ -34,6 +35,7 @@ struct TiledSpec {
     int block;
     int group;
     Filter filter;
+    bool linear = false;  // the linear sink (rt2_render_linear; rt2_path.h end_path_linear)
 };
 // TILED: triangles streamed through LDS in tiles of p.tile_tris (coalesced
 // 16-B loads); the workgroup sweeps each tile in lockstep, so one tile serves
@@ -46,7 +48,7 @@ __global__ __launch_bounds__(S.block) void render_tiled(RenderParams p) {
     lane_init(L);
     const int T = p.tile_tris;
     for (;;) {
-        advance(L, p);
+        advance<1, true, false, false, S.linear>(L, p);
         if (threadIdx.x == 0) block_any = 0;
         __syncthreads();
         if (L.st == ST_TRACE) block_any = 1;
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(S.block) void render_tiled(RenderParams p) {
         if (tracing) {
             L.bounce += 1;
             L.segs += 1;
-            shade(L, p, best, bi);
+            shade<1, false, S.linear>(L, p, best, bi);
         }
     }
     flush_counters(L, p);
@@ -85,7 +87,7 @@ __device__ __forceinline__ void smem_body(const RenderParams& p) {
     Lane L;
     lane_init(L);
     for (;;) {
-        advance(L, p);
+        advance<1, true, false, false, S.linear>(L, p);
         const unsigned long long act = __ballot(L.st == ST_TRACE);
         if constexpr (S.lockstep) {
             if (!__syncthreads_or(act != 0)) break;
@@ -101,7 +103,7 @@ __device__ __forceinline__ void smem_body(const RenderParams& p) {
                 if (L.st == ST_TRACE) {
                     L.bounce += 1;
                     L.segs += 1;
-                    shade(L, p, b, bidx);
+                    shade<1, false, S.linear>(L, p, b, bidx);
                 }
                 continue;
             }
@@ -127,7 +129,7 @@ __device__ __forceinline__ void smem_body(const RenderParams& p) {
                 if (L.st == ST_TRACE) {
                     L.bounce += 1;
                     L.segs += 1;
-                    shade(L, p, mybest, mybi);
+                    shade<1, false, S.linear>(L, p, mybest, mybi);
                 }
                 continue;
             }
@@ -151,7 +153,7 @@ __device__ __forceinline__ void smem_body(const RenderParams& p) {
                 sweep_masked<S.group, true, S.filter, S.stats>(o, d, nullptr, (const float*)p.tri, p.n_tris, 0, best,
                                                                bi, bestK, &fs);
             }
-            shade(L, p, best, bi);
+            shade<1, false, S.linear>(L, p, best, bi);
         }
     }
     if constexpr (S.stats) fs.flush(p.seg_counter + 20);

@@ -18,6 +18,7 @@ struct Bvh3Spec {
     Slab slab;
     int waves;   // minimum waves per SIMD the register allocation must allow (1 = unconstrained)
     bool diag;   // diagnostic build: occupancy tallies of the traversal loop
+    bool linear = false;  // the linear sink (rt2_render_linear; rt2_path.h end_path_linear)
 };
 struct Bvh2Spec {
     int block;
@@ -689,10 +690,10 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
     uint32_t tests = 0, visits = 0;
     for (;;) {
         if (T.state < 0) {
-            shade(L, p, T.best, T.bi);
+            shade<1, false, S.linear>(L, p, T.best, T.bi);
             T.state = 0;
         }
-        advance(L, p);
+        advance<1, true, false, false, S.linear>(L, p);
         if (L.st == ST_TRACE && T.state == 0) begin_segment4(L, T, p.bvh_root);
         if (!__any(T.state > 0)) break;
         const bool fast = p.recs_ok && __all(T.fast || T.state <= 0);

@@ -966,13 +966,13 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
             static_assert(no_t1 && S.lean && NW <= kResGroups, "cam_park parks in T1 pieces that nothing else uses");
             float4* park = reinterpret_cast<float4*>(&rs.rec[(4 * wave + 3) * 64 + (int)lane_id()]);
             if constexpr (S.diag)
-                advance<1, false, true, true>(L, p, park, pds.get());
+                advance<1, false, true, true, S.linear>(L, p, park, pds.get());
             else
-                advance<1, false, true>(L, p, park);
+                advance<1, false, true, false, S.linear>(L, p, park);
         } else if constexpr (S.diag) {
-            advance<1, !S.lean, false, true>(L, p, nullptr, pds.get());
+            advance<1, !S.lean, false, true, S.linear>(L, p, nullptr, pds.get());
         } else {
-            advance<1, !S.lean>(L, p);
+            advance<1, !S.lean, false, false, S.linear>(L, p);
         }
         unsigned long long act = __ballot(L.st == ST_TRACE);
         if constexpr (S.lean) segs_w += (unsigned long long)__popcll(act);
@@ -996,9 +996,9 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
                 L.bounce += 1;
                 if constexpr (!S.lean) L.segs += 1;
                 if constexpr (S.diag)
-                    shade<1, true>(L, p, mybest, mybi, pds.get());
+                    shade<1, true, S.linear>(L, p, mybest, mybi, pds.get());
                 else
-                    shade(L, p, mybest, mybi);
+                    shade<1, false, S.linear>(L, p, mybest, mybi);
             }
             continue;
         }
@@ -1069,9 +1069,9 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
             L.bounce += 1;
             if constexpr (!S.lean) L.segs += 1;
             if constexpr (S.diag)
-                shade<1, true>(L, p, best, bi, pds.get());
+                shade<1, true, S.linear>(L, p, best, bi, pds.get());
             else
-                shade(L, p, best, bi);
+                shade<1, false, S.linear>(L, p, best, bi);
         }
     }
     const RenderParams& p = kargs<RenderParams>();

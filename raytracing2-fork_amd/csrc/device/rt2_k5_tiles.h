@@ -236,7 +236,7 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
     [[maybe_unused]] unsigned long long segs_w = 0;
     for (;;) {
         const RenderParams& p = kargs<RenderParams>();
-        advance<1, !S.lean>(L, p);
+        advance<1, !S.lean, false, false, S.linear>(L, p);
         unsigned long long act = __ballot(L.st == ST_TRACE);
         if (!block_any<NW>(act != 0, vote, vote_parity)) break;
         if constexpr (S.lean) segs_w += (unsigned long long)__popcll(act);
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
             if (mine) {
                 L.bounce += 1;
                 if constexpr (!S.lean) L.segs += 1;
-                shade(L, p, mybest, mybi);
+                shade<1, false, S.linear>(L, p, mybest, mybi);
             }
             continue;
         }
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
         if (mine) {
             L.bounce += 1;
             if constexpr (!S.lean) L.segs += 1;
-            shade(L, p, best, bi);
+            shade<1, false, S.linear>(L, p, best, bi);
         }
     }
     // a share of the next segment's first tiles may still be in flight; it

@@ -88,6 +88,7 @@ struct MfmaSpec {
                               // (records, table, triangles and slot_tri of the triangles in slot order); the episode
                               // breaks distance ties by the triangles' indices and the sweep returns an index
                               // (rt2_k5_resident.h slot_image; DESIGN.md "Slot order")
+    bool linear = false;  // the linear sink (rt2_render_linear; rt2_path.h end_path_linear)
 };
 
 // per-wave diagnostic counts (wave-uniform; MfmaSpec::diag)
@@ -969,7 +970,7 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
         // loads) in every segment instead of being held in SGPRs across the
         // sweep (whose register pressure then spills them to VGPR lanes)
         const RenderParams& p = kargs<RenderParams>();
-        advance(L, p);
+        advance<1, true, false, false, S.linear>(L, p);
         unsigned long long act = __ballot(L.st == ST_TRACE);
         if (!block_any<S.block / 64>(act != 0, vote, vote_parity)) break;
         if (!act) continue;
@@ -980,7 +981,7 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
             if (L.st == ST_TRACE) {
                 L.bounce += 1;
                 L.segs += 1;
-                shade(L, p, mybest, mybi);
+                shade<1, false, S.linear>(L, p, mybest, mybi);
             }
             continue;
         }
@@ -1029,7 +1030,7 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
         if (mine) {
             L.bounce += 1;
             L.segs += 1;
-            shade(L, p, best, bi);
+            shade<1, false, S.linear>(L, p, best, bi);
         }
     }
     flush_counters(L, p_arg);

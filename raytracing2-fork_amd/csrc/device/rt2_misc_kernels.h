@@ -297,6 +297,15 @@ __global__ void resolve_kernel(const float4* acc, long long n, float inv_frames_
     out[i] = make_float4(a.x / frames, a.y / frames, a.z / frames, 1.0f);
 }
 
+// rt2_resolve_tonemap: a linear sum (rt2_render_linear) to the display value
+// end_path gives a frame's mean: the same division, aces1 and srgb1.
+__global__ void resolve_tonemap_kernel(const float4* lin, long long n, float frames, float4* out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = lin[i];
+    out[i] = make_float4(srgb1(aces1(a.x / frames)), srgb1(aces1(a.y / frames)), srgb1(aces1(a.z / frames)), 1.0f);
+}
+
 // The reference screenshot's 8-bit average (rayTracing.cpp:248-250) on the
 // device: u8(min(255, float(sum) / frames)) per channel, rgba sums -> rgb
 // bytes; the same operations as the host rt2_resolve_rgb8_reference.

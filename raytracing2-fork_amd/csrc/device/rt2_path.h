@@ -52,7 +52,10 @@ template <int S = 1>
 __device__ __forceinline__ bool split_writer() {
     return S == 1 || threadIdx.x < 64;
 }
-template <int S = 1>
+// LIN: the linear sink (rt2_render_linear; a kernel spec's `linear`): the frame's
+// mean goes out without the tonemap and the samples' squares are summed in the
+// item's own slot of a moment plane (end_path_linear).
+template <int S = 1, bool LIN = false>
 __device__ __forceinline__ void end_path(Lane& L, const RenderParams& p);
 
 // The pixel of item `item` (row-major in the slab; rows interleaved over
@@ -82,7 +85,7 @@ __device__ __forceinline__ f3 camera_end_point(int x, int y, const RenderParams&
 // of LDS that belong to this lane alone; each of the pixel's rays reads it
 // back.  The same operations on the same inputs, so the same bits.  A caller
 // that moves path states between lanes moves the parked value with them.
-template <int S = 1, bool XY = true, bool PARK = false, bool PD = false>
+template <int S = 1, bool XY = true, bool PARK = false, bool PD = false, bool LIN = false>
 __device__ __forceinline__ void advance(Lane& L, const RenderParams& p, float4* park = nullptr,
                                         PathDiag* pd = nullptr) {
     static_assert(!PARK || !XY, "the parked end point replaces the per-ray recomputation of advance<S, false>");
@@ -189,7 +192,7 @@ __device__ __forceinline__ void advance(Lane& L, const RenderParams& p, float4* 
             L.incoming = mk(0.0f, 0.0f, 0.0f);
             L.bounce = 0;
             L.st = ST_TRACE;
-            if (p.maxBounce <= 0) end_path<S>(L, p);  // trace() returns 0 without tracing
+            if (p.maxBounce <= 0) end_path<S, LIN>(L, p);  // trace() returns 0 without tracing
         }
         if (!__any(L.st != ST_TRACE && L.st != ST_DONE)) break;
     }
@@ -198,7 +201,13 @@ __device__ __forceinline__ void advance(Lane& L, const RenderParams& p, float4* 
 // End of a path: colorCumulative += trace(...) (compute.glsl:692); next ray,
 // or end of the frame (compute.glsl:696-700 + the screenshot accumulation).
 template <int S>
+__device__ __forceinline__ void end_path_linear(Lane& L, const RenderParams& p);
+template <int S, bool LIN>
 __device__ __forceinline__ void end_path(Lane& L, const RenderParams& p) {
+    if constexpr (LIN) {
+        end_path_linear<S>(L, p);
+        return;
+    }
     L.colorCum = add(L.colorCum, L.incoming);
     L.ray += 1;
     if (L.ray < p.R) {
@@ -226,6 +235,78 @@ __device__ __forceinline__ void end_path(Lane& L, const RenderParams& p) {
                                           q.y + (uint32_t)(clampf(c.y, 0.0f, 1.0f) * 255.0f + 0.5f),
                                           q.z + (uint32_t)(clampf(c.z, 0.0f, 1.0f) * 255.0f + 0.5f), 0u);
         }
+    }
+    L.frame += 1;
+    L.st = L.frame < p.frame_count ? ST_NEW_FRAME : ST_NEED_ITEM;
+    if (L.st == ST_NEED_ITEM && writer && p.cost_out)
+        p.cost_out[L.item] = (uint32_t)__builtin_amdgcn_s_memtime() - p.cost_out[L.item];
+}
+
+// end_path of the linear sink (rt2.h, rt2_render_linear): the same ray count
+// and states, the frame's mean m = colorCum / R written as it is (no aces1 /
+// srgb1, no accum8), and the samples' squares.  q = sum v_s * v_s is kept out
+// of the lane state (no register travels with a path through lane_permute or
+// the sweeps): a pixel-frame has one writer at a time and its samples end in
+// order, so each finished path adds its square to the item's own 16-byte slot
+// of a moment plane (one per frame under frame_split, else one plane that
+// sample 0 of every frame starts over: no read), and the last sample turns the
+// slot's sum into m2 = q / R.  A path state that moved to another lane of its
+// wave finds the slot by its item; the wave's own earlier store is visible to
+// it (one wave's vector memory operations reach the CU's cache in order).
+// Product rounded, then the sum: __fmul_rn / __fadd_rn never contract.
+//
+// The sink adds no kernel argument: RenderParams' size and offsets are part of
+// every kernel's code (the queries' second argument lies behind it), and the
+// existing kernels keep theirs.  A linear render has no 8-bit sums, so accum8
+// carries d_sumsq (float4 records, nullable), and the moment planes lie in the
+// frame scratch: behind the frame_count colour planes under frame_split, else
+// the scratch's one plane.
+__device__ __forceinline__ float4* lin_accum_sq(const RenderParams& p) { return reinterpret_cast<float4*>(p.accum8); }
+__device__ __forceinline__ float4* lin_moment_slot(const RenderParams& p, uint32_t frame, uint32_t item) {
+    return p.frame_buf + (p.frame_split ? ((size_t)p.frame_count + frame) * p.n_pix : (size_t)0) + item;
+}
+template <int S>
+__device__ __forceinline__ void end_path_linear(Lane& L, const RenderParams& p) {
+    const bool writer = split_writer<S>();
+    float4* const accum_sq = lin_accum_sq(p);
+    if (accum_sq) {  // a kernel argument: wave-uniform
+        if (writer) {
+            float4* slot = lin_moment_slot(p, L.frame, L.item);
+            float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (L.ray != 0) q = *slot;
+            q.x = __fadd_rn(q.x, __fmul_rn(L.incoming.x, L.incoming.x));
+            q.y = __fadd_rn(q.y, __fmul_rn(L.incoming.y, L.incoming.y));
+            q.z = __fadd_rn(q.z, __fmul_rn(L.incoming.z, L.incoming.z));
+            if (L.ray + 1 < p.R) {
+                *slot = q;
+            } else {
+                const f3 m2 = divs(mk(q.x, q.y, q.z), (float)p.R);
+                if (p.frame_split) {  // frame_accumulate adds the frames' m2 in order afterwards
+                    *slot = make_float4(m2.x, m2.y, m2.z, 0.0f);
+                } else {
+                    const float4 a = accum_sq[L.item];
+                    accum_sq[L.item] = make_float4(a.x + m2.x, a.y + m2.y, a.z + m2.z, 0.0f);
+                }
+            }
+        }
+    }
+    L.colorCum = add(L.colorCum, L.incoming);
+    L.ray += 1;
+    if (L.ray < p.R) {
+        L.st = ST_NEW_RAY;
+        return;
+    }
+    const f3 c = divs(L.colorCum, (float)p.R);
+    if (p.frame_split) {
+        if (writer) p.frame_buf[(size_t)L.frame * p.n_pix + L.item] = make_float4(c.x, c.y, c.z, 0.0f);
+        if (writer && p.cost_out && L.frame == 0)
+            p.cost_out[L.item] = (uint32_t)__builtin_amdgcn_s_memtime() - p.cost_out[L.item];
+        L.st = ST_NEED_ITEM;
+        return;
+    }
+    if (writer) {
+        const float4 a = p.accum[L.item];
+        p.accum[L.item] = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, 0.0f);
     }
     L.frame += 1;
     L.st = L.frame < p.frame_count ? ST_NEW_FRAME : ST_NEED_ITEM;
@@ -293,7 +374,7 @@ __device__ __forceinline__ f3 shade_rnd_dir(uint32_t& seed, PathDiag* pd) {
         return rnd_dir(seed);
     }
 }
-template <int S = 1, bool PD = false>
+template <int S = 1, bool PD = false, bool LIN = false>
 __device__ __forceinline__ void shade(Lane& L, const RenderParams& p, float best, int bi, PathDiag* pd = nullptr) {
     if (bi >= 0) {
         const int mi = p.tri_mtl[bi];
@@ -328,7 +409,7 @@ __device__ __forceinline__ void shade(Lane& L, const RenderParams& p, float best
         case RT2_LIGHT: {
             f3 emitted = muls(xyz4(m.emissionColor), m.emissionStrength);
             L.incoming = add(L.incoming, mul(emitted, L.rayColor));
-            end_path<S>(L, p);
+            end_path<S, LIN>(L, p);
             return;
         }
         case RT2_CHECKER: {
@@ -353,7 +434,7 @@ __device__ __forceinline__ void shade(Lane& L, const RenderParams& p, float best
         }
         default:  // GLASS_HIGHLIGHT and unknown types: trace() returns magenta
             L.incoming = mk(1.0f, 0.0f, 1.0f);
-            end_path<S>(L, p);
+            end_path<S, LIN>(L, p);
             return;
         }
         if (m.isEdgeHighlight && L.bounce > 1)
@@ -362,14 +443,14 @@ __device__ __forceinline__ void shade(Lane& L, const RenderParams& p, float best
             L.rayColor = mul(L.rayColor, atten);
         float pr = fmaxf(L.rayColor.x, fmaxf(L.rayColor.y, L.rayColor.z));
         if (rnd(L.seed) > pr) {
-            end_path<S>(L, p);
+            end_path<S, LIN>(L, p);
             return;
         }
         L.rayColor = muls(L.rayColor, 1.0f / pr);
-        if (L.bounce >= p.maxBounce) end_path<S>(L, p);
+        if (L.bounce >= p.maxBounce) end_path<S, LIN>(L, p);
     } else {
         if (p.envLight) L.incoming = add(L.incoming, mul(sky(L.d), L.rayColor));
-        end_path<S>(L, p);
+        end_path<S, LIN>(L, p);
     }
 }
 

@@ -95,7 +95,7 @@ struct rt2_scene {
     rt2_cluster_table slot_table = {};          // ... its table over the slot groups
     std::vector<int32_t> slot_tri;              // ... slot s holds triangle slot_tri[s]
     float mfma_A = 0.0f;                        // max |a_i| over the in-range triangles
-    float4* d_fb = nullptr;                     // frame_split scratch (per-frame colours)
+    float4* d_fb = nullptr;                     // frame_split scratch (per-frame colours; linear renders: moment slots)
     uchar4* d_texels = nullptr;                 // textures, RGBA8
     int4* d_tex_desc = nullptr;
     int n_tex = 0;
@@ -131,6 +131,9 @@ struct rt2_scene {
     uint4* d_host_acc8 = nullptr;   // 8-bit path sums
     uint8_t* d_host_rgb8 = nullptr; // 8-bit path result (3 B per pixel)
     size_t host_cap = 0;            // pixels the four buffers hold
+    // rt2_render_linear_host: sums, second moments and their two resolved means, kept like the above
+    float4* d_lin[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t lin_cap = 0;             // pixels each of the four holds
     // rt2_trace_rays_host: staging buffers, kept like the above
     rt2_ray* d_query_rays = nullptr;
     rt2_hit* d_query_hits = nullptr;
@@ -577,6 +580,7 @@ extern "C" void rt2_scene_destroy(rt2_scene* s) {
     (void)hipFree(s->d_mfma_kt);
     (void)hipFree(s->d_slot);
     (void)hipFree(s->d_fb);
+    for (float4* b : s->d_lin) (void)hipFree(b);
     (void)hipFree(s->d_cost);
     (void)hipFree(s->d_order);
     (void)hipFree(s->d_hist);
@@ -639,6 +643,15 @@ struct Variant {
     int max_groups = 0;  // largest scene the kernel holds, in 32-triangle groups (0 = no limit)
     bool slot = false;   // MfmaSpec::slot_order: RenderParams::mfma_kt_frag is the scene's slot image
 };
+
+// Linear twins (rt2_render_linear): variant id + kLinearTwin is the same kernel template on the same spec with
+// `linear` set, i.e. the same schedule and sweeps with end_path_linear as the sink (rt2_path.h).
+constexpr int kLinearTwin = 1000;
+template <class Spec>
+constexpr Spec lin(Spec x) {
+    x.linear = true;
+    return x;
+}
 
 template <auto K, int BLOCK>
 hipError_t launch_k(const RenderParams& p, int blocks, size_t lds, hipStream_t st) {
@@ -780,6 +793,17 @@ constexpr Variant kVariants[] = {
     // the default above 8,192 triangles: the LDS-tiled kernel (rt2_k5_tiles.h; 19-group tiles, fragments in
     // registers) with the threshold in the K-slots, each ray's own W in the bound
     RT2_VARIANT(380, K_MFMA, render_mfma_k5t<kt_tiles_flow4()>, 1024, "mfmat5/1024/kt4/tile19/coop0/w4/cmp/regs/perm/lw/flowp/lean"),
+    // the linear twins of every variant above (kLinearTwin; 0's is 136's)
+    RT2_VARIANT(1109, K_BVH4, render_bvh4<lin(kBvhDefault)>, 256, "bvh4/256/t16/w5/lin"),
+    RT2_VARIANT(1086, K_TILED, render_tiled<lin(kTiledLarge)>, 512, "tiled/512/max3f4/lin"),
+    RT2_VARIANT(1092, K_ASSIST, render_assist<lin(kAssist12)>, 768, "assist12/max3f8/w6/lin"),
+    RT2_VARIANT(1136, K_SMEM, render_smem<lin(kSmemDefault)>, 256, "smem/256/max3f8/coop32/w6/lockstep/lin"),
+    RT2_VARIANT(1227, K_MFMA, render_mfma<lin(kMfmaK5)>, 256, "mfma/256/k5/coop8/w3/imax/minred/ymma/t12/llds/ser4/cmp/lin"),
+    RT2_VARIANT(1353, K_MFMA, render_mfma_k5r<lin(kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/lin", kResGroups, true),
+    RT2_VARIANT(1354, K_MFMA, render_mfma_k5r<lin(kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin))))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/lin", kResGroups, true),
+    RT2_VARIANT(1355, K_MFMA, render_mfma_k5r<lin(kt_win(kt_res(true, false, true, 4), kResWin))>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4/lin", kResL2Groups),
+    RT2_VARIANT(1356, K_MFMA, render_mfma_k5r<lin(kt_win(kt_res(true, true, true), kResWin))>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw/lin", kResL2Groups),
+    RT2_VARIANT(1380, K_MFMA, render_mfma_k5t<lin(kt_tiles_flow4())>, 1024, "mfmat5/1024/kt4/tile19/coop0/w4/cmp/regs/perm/lw/flowp/lean/lin"),
 #ifdef RT2_EXPERIMENTS
     // One knob away from a shipping matrix-filter kernel, plus one diagnostic build per template (DESIGN.md "Tried
     // and measured"; earlier generations are in git history).
@@ -912,6 +936,8 @@ const Variant* find_variant(int id) {
         if (v.id == id) return &v;
     return nullptr;
 }
+// The twin rt2_render_linear launches in place of v (null: v has none); the automatic id 0 is 136's kernel.
+const Variant* linear_twin(const Variant& v) { return find_variant(kLinearTwin + (v.id == 0 ? 136 : v.id)); }
 hipError_t variant_occupancy(const Variant& v, int* occ, size_t lds) {
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, reinterpret_cast<const void*>(v.kernel), v.block, lds);
 }
@@ -925,6 +951,11 @@ extern "C" int rt2_scene_set_variant(rt2_scene* s, int variant) {
     if (variant != 0 && !find_variant(variant)) {
         rt2h::set_error("rt2_scene_set_variant: variant " + std::to_string(variant) +
                         " is not in this build (experiment variants need make EXPERIMENTS=1)");
+        return -1;
+    }
+    if (variant >= kLinearTwin) {
+        rt2h::set_error("rt2_scene_set_variant: variant " + std::to_string(variant) +
+                        " is a linear twin: set its parent, rt2_render_linear launches the twin");
         return -1;
     }
     s->variant = variant;
@@ -951,33 +982,27 @@ extern "C" int rt2_variant_occupancy(int v, int* api_blocks, int* num_regs, int*
     return 0;
 }
 
-extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count,
-                          rt2_shard sh, float* d_accum, uint32_t* d_accum8, void* stream) {
-    if (!s || !u || !d_accum) {
-        rt2h::set_error("rt2_render: null argument");
-        return -1;
-    }
-    if ((!u->basicShading && u->numRaysPerPixel < 1) || u->width < 1 || u->height < 1) {
-        rt2h::set_error("rt2_render: numRaysPerPixel, width and height must be >= 1");
-        return -1;
-    }
+// rt2_render (linear = false: d_sumsq is null) and rt2_render_linear (linear =
+// true: d_accum is d_sum, d_accum8 null) after their argument checks: one
+// selection logic, one schedule; the linear render launches the chosen
+// variant's twin (id + kLinearTwin) and folds a second set of frame planes.
+static int render_launch(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count, rt2_shard sh,
+                         float* d_accum, uint32_t* d_accum8, float* d_sumsq, bool linear, void* stream) {
     const int rows = rt2_shard_rows((int)u->height, sh);
-    if (rows < 0) {
-        rt2h::set_error("rt2_render: bad shard");
-        return -1;
-    }
-    if (frame_count == 0 || rows == 0) return 0;
     // frame-major items keep one colour plane per frame: beyond frame_scratch_cap
     // of planes (or 2^32 items), render consecutive frame chunks — the
     // accumulation stays in frame order, so the sums are unchanged
     if (!u->basicShading && s->split_frames && frame_count > 1) {
         const unsigned long long npix = (unsigned long long)rows * u->width;
-        unsigned long long chunk = std::max<unsigned long long>(1, s->frame_scratch_cap / (npix * sizeof(float4)));
+        // (a linear render with moments keeps two planes per frame)
+        const unsigned long long per_frame = npix * sizeof(float4) * (d_sumsq ? 2u : 1u);
+        unsigned long long chunk = std::max<unsigned long long>(1, s->frame_scratch_cap / per_frame);
         chunk = std::min<unsigned long long>(chunk, 0xfffffffeull / std::max<unsigned long long>(npix, 1));
         if (chunk < frame_count) {
             for (unsigned long long f0 = 0; f0 < frame_count; f0 += chunk) {
                 const uint32_t fc = (uint32_t)std::min<unsigned long long>(chunk, frame_count - f0);
-                const int rc = rt2_render(s, u, frame_begin + (uint32_t)f0, fc, sh, d_accum, d_accum8, stream);
+                const int rc = render_launch(s, u, frame_begin + (uint32_t)f0, fc, sh, d_accum, d_accum8, d_sumsq,
+                                             linear, stream);
                 if (rc != 0) return rc;
             }
             return 0;
@@ -1036,7 +1061,8 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
         return -1;
     }
     p.accum = reinterpret_cast<float4*>(d_accum);
-    p.accum8 = reinterpret_cast<uint4*>(d_accum8);
+    // the linear sink never writes 8-bit sums: its kernels read d_sumsq from this field (lin_accum_sq)
+    p.accum8 = linear ? reinterpret_cast<uint4*>(d_sumsq) : reinterpret_cast<uint4*>(d_accum8);
     p.item_counter = s->d_counters;
     p.seg_counter = s->d_counters + 1;
     p.tile_tris = kTileTris;
@@ -1085,7 +1111,8 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
     // several frames: frame-major (frame, pixel) items into a scratch buffer,
     // then frame_accumulate (finer work items: a shorter tail)
     if (frame_count > 1 && s->split_frames && p.n_pix * frame_count < 0xffffffffull) {
-        const size_t need = (size_t)p.n_pix * frame_count * sizeof(float4);
+        // (a linear render with moments: the frames' moment planes behind the colour planes)
+        const size_t need = (size_t)p.n_pix * frame_count * sizeof(float4) * (d_sumsq ? 2u : 1u);
         if (need > s->fb_bytes) {
             if (s->d_fb) HIPCHECK(hipFree(s->d_fb));
             s->d_fb = nullptr;
@@ -1096,6 +1123,17 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
         p.frame_split = 1;
         p.frame_buf = s->d_fb;
         p.n_items = p.n_pix * frame_count;
+    }
+    if (d_sumsq && !p.frame_split) {  // the moment slots of whole-pixel items: one plane
+        const size_t need = (size_t)p.n_pix * sizeof(float4);
+        if (need > s->fb_bytes) {
+            if (s->d_fb) HIPCHECK(hipFree(s->d_fb));
+            s->d_fb = nullptr;
+            s->fb_bytes = 0;
+            HIPCHECK(hipMalloc(&s->d_fb, need));
+            s->fb_bytes = need;
+        }
+        p.frame_buf = s->d_fb;
     }
     // cost-ordered items: the previous launch's per-pixel costs (same slab)
     // give this launch's pixel order, most expensive first (a shorter tail)
@@ -1141,6 +1179,7 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
     if (VP && ((s->traversal == RT2_TRAVERSAL_BVH) != is_bvh(VP->kind))) VP = nullptr;
     if (VP && VP->max_groups > 0 && n_groups > VP->max_groups) VP = nullptr;  // cannot hold this scene
     if (VP && VP->kind == K_MFMA && !s->mfma_ok) VP = nullptr;              // scene outside the filter's range
+    if (VP && linear && !linear_twin(*VP)) VP = nullptr;                    // an experiment variant without a twin
     if (!VP && s->traversal == RT2_TRAVERSAL_BVH) VP = find_variant(kDefaultBvh);
     if (!VP) {
         int vi = s->n_tris <= kSmemMaxTris ? kDefaultBrute : kLargeScene;
@@ -1185,6 +1224,7 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
         }
         VP = find_variant(vi);
     }
+    if (linear) VP = linear_twin(*VP);  // every variant chosen above has one
     const Variant& V = *VP;
     // XCD-group item regions serve the BVH walk's L2 locality; the brute-force
     // kernels read the same records for every ray, so they take items from one
@@ -1243,8 +1283,14 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
     HIPCHECK(hipGetLastError());
     if (p.frame_split) {
         hipLaunchKernelGGL(frame_accumulate, dim3((unsigned)((p.n_pix + 255) / 256)), dim3(256), 0, st, p.frame_buf,
-                           p.n_pix, frame_count, p.accum, p.accum8);
+                           p.n_pix, frame_count, p.accum, linear ? (uint4*)nullptr : p.accum8);
         HIPCHECK(hipGetLastError());
+        if (d_sumsq) {  // the frames' second moments, in the same order
+            hipLaunchKernelGGL(frame_accumulate, dim3((unsigned)((p.n_pix + 255) / 256)), dim3(256), 0, st,
+                               p.frame_buf + (size_t)p.n_pix * frame_count, p.n_pix, frame_count,
+                               reinterpret_cast<float4*>(d_sumsq), (uint4*)nullptr);
+            HIPCHECK(hipGetLastError());
+        }
     }
     if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
     HIPCHECK(hipEventRecord(s->last_launch, st));
@@ -1252,6 +1298,25 @@ extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_be
     s->samples += p.n_pix * (unsigned long long)p.R * (unsigned long long)frame_count;
     s->tests_per_seg = (unsigned long long)s->n_tris;
     return 0;
+}
+
+extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count,
+                          rt2_shard sh, float* d_accum, uint32_t* d_accum8, void* stream) {
+    if (!s || !u || !d_accum) {
+        rt2h::set_error("rt2_render: null argument");
+        return -1;
+    }
+    if ((!u->basicShading && u->numRaysPerPixel < 1) || u->width < 1 || u->height < 1) {
+        rt2h::set_error("rt2_render: numRaysPerPixel, width and height must be >= 1");
+        return -1;
+    }
+    const int rows = rt2_shard_rows((int)u->height, sh);
+    if (rows < 0) {
+        rt2h::set_error("rt2_render: bad shard");
+        return -1;
+    }
+    if (frame_count == 0 || rows == 0) return 0;
+    return render_launch(s, u, frame_begin, frame_count, sh, d_accum, d_accum8, nullptr, false, stream);
 }
 
 extern "C" int rt2_scene_stats(rt2_scene* s, rt2_stats* out, int reset) {
@@ -1359,6 +1424,91 @@ extern "C" int rt2_render_host(rt2_scene* s, const rt2_uniforms* u, uint32_t fra
                            s->d_host_acc8, (long long)n, (float)frame_count, s->d_host_rgb8);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipMemcpyAsync(out_rgb8, s->d_host_rgb8, n * 3, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHECK(hipStreamSynchronize(st));  // only this render's stream, not the device
+    return 0;
+}
+
+/* -------------------------------------------------------------------------
+ * Linear renders (rt2_path.h end_path_linear; the twins of kVariants)
+ * ----------------------------------------------------------------------- */
+// The argument checks of rt2_render_linear (device = true: the pointers'
+// alignment too) and rt2_render_linear_host; *rows = the slab's rows.
+static int render_linear_args(const char* fn, const rt2_scene* s, const rt2_uniforms* u, rt2_shard sh,
+                              const float* sum, const float* sumsq, bool device, int* rows) {
+    const auto bad = [&](const char* what) {
+        rt2h::set_error(std::string(fn) + ": bad argument: " + what);
+        return -1;
+    };
+    if (!s) return bad("null scene");
+    if (!u) return bad("null uniforms");
+    if (!sum) return bad(device ? "null d_sum" : "null out_mean");
+    if (device && (reinterpret_cast<uintptr_t>(sum) % 16 != 0 || reinterpret_cast<uintptr_t>(sumsq) % 16 != 0))
+        return bad("d_sum and d_sumsq must be aligned to 16 bytes");
+    if (u->basicShading) return bad("basicShading: the preview has no tonemap, rt2_render gives its linear value");
+    if (u->numRaysPerPixel < 1) return bad("numRaysPerPixel must be >= 1");
+    if (u->width < 1 || u->height < 1) return bad("width and height must be >= 1");
+    *rows = rt2_shard_rows((int)u->height, sh);
+    if (*rows < 0) return bad("bad shard");
+    return 0;
+}
+
+extern "C" int rt2_render_linear(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count,
+                                 rt2_shard sh, float* d_sum, float* d_sumsq, void* stream) {
+    int rows = 0;
+    if (render_linear_args("rt2_render_linear", s, u, sh, d_sum, d_sumsq, true, &rows) != 0) return -1;
+    if (frame_count == 0 || rows == 0) return 0;
+    return render_launch(s, u, frame_begin, frame_count, sh, d_sum, nullptr, d_sumsq, true, stream);
+}
+
+extern "C" int rt2_resolve_tonemap(const float* d_linear_sum, int64_t n, uint32_t frames, float* d_out, void* stream) {
+    if (!d_linear_sum || !d_out || n < 0 || frames == 0) {
+        rt2h::set_error("rt2_resolve_tonemap: bad argument");
+        return -1;
+    }
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(resolve_tonemap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(d_linear_sum), (long long)n, (float)frames,
+                       reinterpret_cast<float4*>(d_out));
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int rt2_render_linear_host(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count,
+                                      rt2_shard sh, float* out_mean, float* out_meansq) {
+    int rows = 0;
+    if (render_linear_args("rt2_render_linear_host", s, u, sh, out_mean, out_meansq, false, &rows) != 0) return -1;
+    const size_t n = (size_t)rows * u->width;
+    if (n == 0 || frame_count == 0) return 0;
+    HIPCHECK(hipSetDevice(s->device));
+    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    hipStream_t st = s->host_stream;
+    if (n > s->lin_cap) {  // sums, second moments and their resolved means: grown together, freed with the scene
+        HIPCHECK(hipStreamSynchronize(st));
+        for (float4*& b : s->d_lin) {
+            (void)hipFree(b);
+            b = nullptr;
+        }
+        s->lin_cap = 0;
+        for (float4*& b : s->d_lin) HIPCHECK(hipMalloc(&b, n * sizeof(float4)));
+        s->lin_cap = n;
+    }
+    float4* const d_sum = s->d_lin[0];
+    float4* const d_sq = out_meansq ? s->d_lin[1] : nullptr;
+    HIPCHECK(hipMemsetAsync(d_sum, 0, n * sizeof(float4), st));
+    if (d_sq) HIPCHECK(hipMemsetAsync(d_sq, 0, n * sizeof(float4), st));
+    if (rt2_render_linear(s, u, frame_begin, frame_count, sh, reinterpret_cast<float*>(d_sum),
+                          reinterpret_cast<float*>(d_sq), st) != 0)
+        return -1;
+    if (rt2_resolve_rgba32f(reinterpret_cast<const float*>(d_sum), (int64_t)n, frame_count,
+                            reinterpret_cast<float*>(s->d_lin[2]), st) != 0)
+        return -1;
+    HIPCHECK(hipMemcpyAsync(out_mean, s->d_lin[2], n * sizeof(float4), hipMemcpyDeviceToHost, st));
+    if (d_sq) {
+        if (rt2_resolve_rgba32f(reinterpret_cast<const float*>(d_sq), (int64_t)n, frame_count,
+                                reinterpret_cast<float*>(s->d_lin[3]), st) != 0)
+            return -1;
+        HIPCHECK(hipMemcpyAsync(out_meansq, s->d_lin[3], n * sizeof(float4), hipMemcpyDeviceToHost, st));
     }
     HIPCHECK(hipStreamSynchronize(st));  // only this render's stream, not the device
     return 0;

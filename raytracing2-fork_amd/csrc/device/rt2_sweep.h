@@ -41,8 +41,9 @@ struct RenderParams {
     uint32_t n_runs;             // full 64-pixel runs covered by `order` (the partial last run keeps its place)
     uint32_t* cost_out;          // nullable: per-pixel item cost (shader clocks) for the next launch's order
     float4* frame_buf;           // frame_split: [frame_count][n_pix] per-frame colours
+                                 // (the linear sink: its moment slots too, rt2_path.h lin_moment_slot)
     float4* accum;
-    uint4* accum8;
+    uint4* accum8;               // (the linear sink: d_sumsq, nullable, rt2_path.h lin_accum_sq)
     unsigned long long* item_counter;
     unsigned long long* region_ctr;  // nullable: 8 item-region counters, 128 B apart (XCD-group regions)
     unsigned long long* seg_counter;

@@ -185,6 +185,7 @@ SHADE_RES, SHADE_RES_L2, SHADE_SCALAR, SHADE_BVH = -14, -15, -16, -17  # ... aft
 SHADED_DTYPE = np.dtype([("rgb", "<f4", 3), ("segments", "<i4")])
 assert SHADED_DTYPE.itemsize == 16
 RADIANCE_RES, RADIANCE_RES_L2, RADIANCE_SCALAR, RADIANCE_BVH = -18, -19, -20, -21  # ... after a radiance query
+LINEAR_TWIN = 1000  # ... after a linear render: the variant's id + LINEAR_TWIN (1136 for the automatic 0)
 # rt2_radiance (radiance queries): trace()'s linear colour and the closest-hit searches the path cost
 RADIANCE_DTYPE = np.dtype([("rgb", "<f4", 3), ("segments", "<i4")])
 assert RADIANCE_DTYPE.itemsize == 16 and C.sizeof(PathOpts) == 16
@@ -208,6 +209,7 @@ EXPORTED = [
     "rt2_surface_rays", "rt2_surface_rays_host", "rt2_camera_rays", "rt2_camera_rays_host",
     "rt2_shade_rays", "rt2_shade_rays_host",
     "rt2_radiance_rays", "rt2_radiance_rays_host", "rt2_path_rays", "rt2_path_rays_host",
+    "rt2_render_linear", "rt2_render_linear_host", "rt2_resolve_tonemap",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -261,6 +263,9 @@ def lib() -> C.CDLL:
         "rt2_path_rays_host": (C.c_int, [P, C.POINTER(Uniforms), Shard, U32, C.c_int, P, P]),
         "rt2_camera_rays": (C.c_int, [P, C.POINTER(Uniforms), Shard, P, P]),
         "rt2_camera_rays_host": (C.c_int, [P, C.POINTER(Uniforms), Shard, P]),
+        "rt2_render_linear": (C.c_int, [P, C.POINTER(Uniforms), U32, U32, Shard, P, P, P]),
+        "rt2_render_linear_host": (C.c_int, [P, C.POINTER(Uniforms), U32, U32, Shard, P, P]),
+        "rt2_resolve_tonemap": (C.c_int, [P, I64, U32, P, P]),
         "rt2_resolve_rgba32f": (C.c_int, [P, I64, U32, P, P]),
         "rt2_resolve_rgb8_reference": (C.c_int, [P, I64, U32, P]),
         "rt2_scene_stats": (C.c_int, [P, C.POINTER(Stats), C.c_int]),
@@ -645,6 +650,30 @@ class Scene:
                                      None if out8 is None else out8.ctypes.data), "rt2_render_host")
         return (out, out8) if rgb8 else out
 
+    def render_linear(self, u: Uniforms, frame_begin: int, frame_count: int, sh: Shard, sum_ptr: int,
+                      sumsq_ptr: int = 0, stream: int = 0) -> None:
+        """Asynchronous linear render (rt2_render_linear): render()'s paths on the chosen kernel's linear twin
+        (last_kernel() = the variant's id + LINEAR_TWIN), the frames' linear means added to the device array at
+        sum_ptr and, with sumsq_ptr, the means of the samples' squares to that one ((rows, W, 4) float32 each,
+        aligned to 16 bytes, .w written 0)."""
+        _check(lib().rt2_render_linear(self._p, C.byref(u), frame_begin, frame_count, sh, C.c_void_p(sum_ptr),
+                                       C.c_void_p(sumsq_ptr) if sumsq_ptr else None,
+                                       C.c_void_p(stream) if stream else None), "rt2_render_linear")
+
+    def render_linear_host(self, u: Uniforms, frame_begin: int, frame_count: int, sh: Optional[Shard] = None,
+                           moments: bool = False):
+        """Blocking linear render (rt2_render_linear_host): the (rows, W, 4) float32 mean over the frames of the
+        per-frame linear means (alpha = 1) — render_host's image before the tonemap and the sRGB encoding — or,
+        with moments, the pair (mean, meansq) with the mean of the samples' squares beside it."""
+        sh = sh or shard()
+        rows = max(shard_rows(u.height, sh), 0)  # a bad shard: the library says so
+        mean = np.zeros((rows, u.width, 4), dtype=np.float32)
+        meansq = np.zeros((rows, u.width, 4), dtype=np.float32) if moments else None
+        _check(lib().rt2_render_linear_host(self._p, C.byref(u), frame_begin, frame_count, sh, mean.ctypes.data,
+                                            None if meansq is None else meansq.ctypes.data),
+               "rt2_render_linear_host")
+        return (mean, meansq) if moments else mean
+
     def render_host_gather(self, u: Uniforms, frame_begin: int, frame_count: int, sh: Shard, comm: "Comm",
                            root: int = 0, rgb8: bool = False):
         """rt2_render_host_gather: this rank's shard, gathered to `root`; returns the
@@ -918,7 +947,9 @@ class Scene:
         in order on the device and divided by numRaysPerPixel in binary32 on
         the host.  Returns ((rows, W, 3) float32, (rows, W) int64 segment
         counts).  u.numTextures is not consulted: a ray query takes the number
-        of images given to set_textures."""
+        of images given to set_textures.  render_linear_host is the fast form
+        of the same image (one launch of the render's own kernel, with
+        u.numTextures as the render uses it)."""
         import torch
 
         sh = sh or shard()
@@ -950,7 +981,8 @@ class Scene:
         return img.reshape(rows, W, 3), segs.reshape(rows, W)
 
     def last_kernel(self) -> int:
-        """What the scene launched last (rt2_scene_diag): a render's variant id (-1: the traceBasic preview), or
+        """What the scene launched last (rt2_scene_diag): a render's variant id (-1: the traceBasic preview; a linear
+        render's: the id + LINEAR_TWIN), or
         after a query QUERY_RES (trace_rays_k5r, every group resident), QUERY_RES_L2 (its L2 continuation),
         QUERY_SCALAR or QUERY_BVH (trace_rays_scalar); after an occlusion query OCCLUDED_RES, OCCLUDED_RES_L2
         (occluded_k5r), OCCLUDED_SCALAR or OCCLUDED_BVH (occluded_scalar); after a surface query SURFACE_RES,
@@ -1093,6 +1125,14 @@ def has_variant(v: int) -> bool:
 def resolve_rgba32f(accum_ptr: int, n_pixels: int, frames: int, out_ptr: int, stream: int = 0) -> None:
     _check(lib().rt2_resolve_rgba32f(C.c_void_p(accum_ptr), n_pixels, frames, C.c_void_p(out_ptr),
                                      C.c_void_p(stream) if stream else None), "resolve")
+
+
+def resolve_tonemap(sum_ptr: int, n_pixels: int, frames: int, out_ptr: int, stream: int = 0) -> None:
+    """Device resolve of a linear sum (Scene.render_linear) to the render's display value: srgb1(aces1(sum /
+    frames)) per channel, alpha = 1 (rt2_resolve_tonemap); asynchronous."""
+    _check(lib().rt2_resolve_tonemap(C.c_void_p(sum_ptr) if sum_ptr else None, n_pixels, frames,
+                                     C.c_void_p(out_ptr) if out_ptr else None,
+                                     C.c_void_p(stream) if stream else None), "rt2_resolve_tonemap")
 
 
 def resolve_rgb8_reference(acc8: np.ndarray, frames: int) -> np.ndarray:
