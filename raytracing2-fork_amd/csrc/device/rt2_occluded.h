@@ -276,17 +276,9 @@ template <OccSpec O>
 __global__ __launch_bounds__(O.m.block) __attribute__((amdgpu_waves_per_eu(O.m.waves))) void occluded_k5r(RenderParams p_arg,
                                                                                                          OccParams q) {
     constexpr MfmaSpec S = O.m;
-    __shared__ K5Resident rs;
-    res_load_records<S>(rs);
-    const int lane = (int)lane_id();
-    const unsigned long long n_chunks = ((unsigned long long)q.n + 63) >> 6;
-    unsigned long long rays_w = 0;
-    const unsigned long long n_waves = (unsigned long long)gridDim.x * (S.block / 64);
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform to the compiler
-    for (unsigned long long c = (unsigned long long)blockIdx.x * (S.block / 64) + wave; c < n_chunks; c += n_waves) {
-        const RenderParams& p = kargs<RenderParams>();
-        const long long base = (long long)(c << 6);
-        const int live = (int)min(64ll, q.n - base);
+    query_chunks<S>(q.n, [&](const RenderParams& p, const h8* rec, long long base, int live, MfmaDiag&,
+                               unsigned long long& segs_w) {
+        const int lane = (int)lane_id();
         const bool mine = lane < live;
         const unsigned long long act = live == 64 ? ~0ull : (1ull << live) - 1ull;
         // lanes of a ragged last chunk carry the chunk's first ray (and its bound)
@@ -295,7 +287,7 @@ __global__ __launch_bounds__(O.m.block) __attribute__((amdgpu_waves_per_eu(O.m.w
         query_load(q.rays, base + (mine ? lane : 0), o, d, bound);
         bool occ = false, swept = false;
         if (!__ballot(!query_finite(o, d)))
-            swept = sweep_kt_occ<O>(p, rs.rec, o, d, bound, bound * 1.0009765625f, live > 32, mine, occ);
+            swept = sweep_kt_occ<O>(p, rec, o, d, bound, bound * 1.0009765625f, live > 32, mine, occ);
         if (!swept) {
             // a ray outside the filter's range or not finite (wave-uniform): the drain's exact code
             float best = bound;
@@ -304,10 +296,8 @@ __global__ __launch_bounds__(O.m.block) __attribute__((amdgpu_waves_per_eu(O.m.w
             occ = bi >= 0;
         }
         if (mine) q.out[base + lane] = occ ? (uint8_t)1 : (uint8_t)0;  // one byte per live lane
-        rays_w += (unsigned long long)live;
-    }
-    const RenderParams& p = kargs<RenderParams>();
-    if (lane == 0) atomicAdd(p.seg_counter, rays_w);
+        segs_w += (unsigned long long)live;
+    });
 }
 
 // calculateRayCollisionBVH (closest_bvh: the same visiting order, the same

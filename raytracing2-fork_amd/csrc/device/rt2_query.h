@@ -58,23 +58,41 @@ __device__ __forceinline__ void query_store(rt2_hit* hits, long long i, float be
     *reinterpret_cast<float2*>(hits + i) = make_float2(best, __int_as_float(bi));  // one 8-B store
 }
 
-template <MfmaSpec S>
-__global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves))) void trace_rays_k5r(RenderParams p_arg,
-                                                                                                         QueryParams q) {
+// The resident chunk frame of the five *_k5r kernels: the resident records into LDS (one barrier), then each wave
+// takes chunks of 64 consecutive rays, a grid stride of waves apart, and lane 0 adds the wave's segments to the
+// launch's counter at the end.  body(p, rec, base, live, dg, segs_w) handles the chunk of `live` rays from ray `base`
+// on and adds its segments to segs_w (the wave's count, by reference and not returned: a returned count is summed
+// in another order, and shade_rays_k5r and radiance_rays_k5r then compile to other code than before the frame was
+// shared).  Returns the sweeps' diagnostic counters (S.diag).
+// (A device-wide chunk counter, one atomic per chunk, held the whole launch to 14 ns per chunk: 2^22 rays took
+// 0.91 ms whatever their sweeps cost.)
+template <MfmaSpec S, class Body>
+__device__ __forceinline__ MfmaDiag query_chunks(long long n, Body body) {
     __shared__ K5Resident rs;
     res_load_records<S>(rs);
     MfmaDiag dg;
     const int lane = (int)lane_id();
-    const unsigned long long n_chunks = ((unsigned long long)q.n + 63) >> 6;
-    unsigned long long rays_w = 0;
-    // A grid stride over the chunks, one wave apart.  (A device-wide counter, one atomic per chunk, held the whole
-    // launch to 14 ns per chunk: 2^22 rays took 0.91 ms whatever their sweeps cost.)
+    const unsigned long long n_chunks = ((unsigned long long)n + 63) >> 6;
+    unsigned long long segs_w = 0;
     const unsigned long long n_waves = (unsigned long long)gridDim.x * (S.block / 64);
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform to the compiler
     for (unsigned long long c = (unsigned long long)blockIdx.x * (S.block / 64) + wave; c < n_chunks; c += n_waves) {
         const RenderParams& p = kargs<RenderParams>();
         const long long base = (long long)(c << 6);
-        const int live = (int)min(64ll, q.n - base);
+        const int live = (int)min(64ll, n - base);
+        body(p, rs.rec, base, live, dg, segs_w);
+    }
+    const RenderParams& p = kargs<RenderParams>();
+    if (lane == 0) atomicAdd(p.seg_counter, segs_w);
+    return dg;
+}
+
+template <MfmaSpec S>
+__global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves))) void trace_rays_k5r(RenderParams p_arg,
+                                                                                                         QueryParams q) {
+    const MfmaDiag sum = query_chunks<S>(q.n, [&](const RenderParams& p, const h8* rec, long long base, int live,
+                                                  MfmaDiag& dg, unsigned long long& segs_w) {
+        const int lane = (int)lane_id();
         const bool mine = lane < live;
         const unsigned long long act = live == 64 ? ~0ull : (1ull << live) - 1ull;
         // lanes of a ragged last chunk carry the chunk's first ray (and its bound)
@@ -84,24 +102,24 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
         float best = bound, bestK = bound * 1.0009765625f;
         int bi = -1;
         bool swept = false;
-        if (!__ballot(!query_finite(o, d))) swept = sweep_kt_res<S>(p, rs.rec, o, d, best, bi, bestK, dg, live > 32);
+        if (!__ballot(!query_finite(o, d))) swept = sweep_kt_res<S>(p, rec, o, d, best, bi, bestK, dg, live > 32);
         // a ray outside the filter's range or not finite (wave-uniform): the drain's exact code
         if (!swept) coop_each(act, o, d, p, best, bi, &bound);
         if (mine) query_store(q.hits, base + lane, best, bi);
-        rays_w += (unsigned long long)live;
-    }
-    const RenderParams& p = kargs<RenderParams>();
-    if (lane == 0) atomicAdd(p.seg_counter, rays_w);
-    if constexpr (S.diag)  // render_mfma_k5r's counter slots (rt2_scene_diag_ex)
-        if (lane == 0) {
-            atomicAdd(p.seg_counter + 1, dg.groups);    // (wave, triangle group) sweeps
-            atomicAdd(p.seg_counter + 2, dg.hot);       // ... with a passing pair
-            atomicAdd(p.seg_counter + 3, dg.exact);     // (wave, triangle) exact tests
-            atomicAdd(p.seg_counter + 12, dg.t_wait);   // shader clocks: the sweep's ray setup
-            atomicAdd(p.seg_counter + 13, dg.t_filt);   // ... products + record reads
-            atomicAdd(p.seg_counter + 14, dg.t_exact);  // ... exact phase
-            atomicAdd(p.seg_counter + 15, dg.t_swp);    // ... whole sweeps
+        segs_w += (unsigned long long)live;
+    });
+    if constexpr (S.diag) {  // render_mfma_k5r's counter slots (rt2_scene_diag_ex)
+        const RenderParams& p = kargs<RenderParams>();
+        if (lane_id() == 0) {
+            atomicAdd(p.seg_counter + 1, sum.groups);    // (wave, triangle group) sweeps
+            atomicAdd(p.seg_counter + 2, sum.hot);       // ... with a passing pair
+            atomicAdd(p.seg_counter + 3, sum.exact);     // (wave, triangle) exact tests
+            atomicAdd(p.seg_counter + 12, sum.t_wait);   // shader clocks: the sweep's ray setup
+            atomicAdd(p.seg_counter + 13, sum.t_filt);   // ... products + record reads
+            atomicAdd(p.seg_counter + 14, sum.t_exact);  // ... exact phase
+            atomicAdd(p.seg_counter + 15, sum.t_swp);    // ... whole sweeps
         }
+    }
 }
 
 // One thread per ray: closest_any's two arms started at the ray's bound.

@@ -144,18 +144,9 @@ template <OccSpec O>
 __global__ __launch_bounds__(O.m.block) __attribute__((amdgpu_waves_per_eu(O.m.waves))) void radiance_rays_k5r(
     RenderParams p_arg, RadianceParams q) {
     constexpr MfmaSpec S = O.m;  // shade_rays_k5r's frame and records
-    __shared__ K5Resident rs;
-    res_load_records<S>(rs);
-    MfmaDiag dg;
-    const int lane = (int)lane_id();
-    const unsigned long long n_chunks = ((unsigned long long)q.n + 63) >> 6;
-    unsigned long long segs_w = 0;
-    const unsigned long long n_waves = (unsigned long long)gridDim.x * (S.block / 64);
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform to the compiler
-    for (unsigned long long c = (unsigned long long)blockIdx.x * (S.block / 64) + wave; c < n_chunks; c += n_waves) {
-        const RenderParams& p = kargs<RenderParams>();
-        const long long base = (long long)(c << 6);
-        const int live = (int)min(64ll, q.n - base);
+    query_chunks<S>(q.n, [&](const RenderParams& p, const h8* rec, long long base, int live, MfmaDiag& dg,
+                             unsigned long long& segs_w) {
+        const int lane = (int)lane_id();
         RadLane L;
         {
             // lanes of a ragged last chunk hold the chunk's first ray and stream and never trace; tmax is not used
@@ -193,7 +184,7 @@ __global__ __launch_bounds__(O.m.block) __attribute__((amdgpu_waves_per_eu(O.m.w
             float best = 1e38f, bestK = 1e38f * 1.0009765625f;
             int bi = -1;
             bool swept = false;
-            if (!__ballot(!query_finite(ro, rd))) swept = sweep_kt_res<S>(p, rs.rec, ro, rd, best, bi, bestK, dg, upper);
+            if (!__ballot(!query_finite(ro, rd))) swept = sweep_kt_res<S>(p, rec, ro, rd, best, bi, bestK, dg, upper);
             // a ray outside the filter's range or not finite (wave-uniform): the drain's exact code
             if (!swept) coop_each(act, ro, rd, p, best, bi);
             if (mine) radiance_step(p, L, best, bi);
@@ -204,9 +195,7 @@ __global__ __launch_bounds__(O.m.block) __attribute__((amdgpu_waves_per_eu(O.m.w
                 make_float4(L.incoming.x, L.incoming.y, L.incoming.z, __int_as_float((int)(L.pk & RD_BOUNCE)));
             q.rng[base + slot] = L.seed;
         }
-    }
-    const RenderParams& p = kargs<RenderParams>();
-    if (lane == 0) atomicAdd(p.seg_counter, segs_w);
+    });
 }
 
 // One thread per ray: trace's loop around closest_any, then the record and the

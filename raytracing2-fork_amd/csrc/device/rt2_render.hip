@@ -68,6 +68,10 @@ void set_error(const std::string& msg);
     } while (0)
 
 constexpr int kCounters = 32;  // [0] items, [1..7] stats + wave-end, [8..] kernel diagnostics
+struct Staging {  // a device buffer grown on demand (staging_grow)
+    void* ptr = nullptr;
+    size_t cap = 0;  // bytes
+};
 struct rt2_scene {
     int device = 0;
     int n_tris = 0, n_mats = 0, n_nodes = 0;
@@ -134,29 +138,12 @@ struct rt2_scene {
     // rt2_render_linear_host: sums, second moments and their two resolved means, kept like the above
     float4* d_lin[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t lin_cap = 0;             // pixels each of the four holds
-    // rt2_trace_rays_host: staging buffers, kept like the above
-    rt2_ray* d_query_rays = nullptr;
-    rt2_hit* d_query_hits = nullptr;
-    size_t query_cap = 0;           // rays the two buffers hold
+    // The ray queries' and ray generators' seven *_host entry points: staging for the rays, the RNG words and the
+    // output bytes, kept like the above.  One set serves them all, because every one of those calls runs on
+    // host_stream and ends in hipStreamSynchronize: no buffer is in use when the next call starts.
+    Staging stage_rays, stage_rng, stage_out;
     int query_arm = 0;                // experiment build: A/B arm of the resident query kernel
-    // rt2_occluded_host: staging buffers, kept like the above
-    rt2_ray* d_occluded_rays = nullptr;
-    uint8_t* d_occluded_out = nullptr;
-    size_t occluded_cap = 0;          // rays the two buffers hold
     int occluded_arm = 0;             // experiment build: A/B arm of occluded_k5r
-    // rt2_surface_rays_host / rt2_camera_rays_host: staging buffers, kept like the above
-    rt2_ray* d_surface_rays = nullptr;
-    rt2_surface* d_surface_out = nullptr;
-    size_t surface_rays_cap = 0, surface_out_cap = 0;  // records each buffer holds
-    // rt2_shade_rays_host: staging buffers, kept like the above
-    rt2_ray* d_shade_rays = nullptr;
-    rt2_shaded* d_shade_out = nullptr;
-    size_t shade_rays_cap = 0, shade_out_cap = 0;      // records each buffer holds
-    // rt2_radiance_rays_host / rt2_path_rays_host: staging buffers, kept like the above
-    rt2_ray* d_radiance_rays = nullptr;
-    uint32_t* d_radiance_rng = nullptr;
-    rt2_radiance* d_radiance_out = nullptr;
-    size_t radiance_rays_cap = 0, radiance_rng_cap = 0, radiance_out_cap = 0;  // records each buffer holds
     unsigned long long* d_region_ctr = nullptr;  // 8 item-region counters, 128 B apart
     unsigned long long* wave_log = nullptr;  // diagnostic wave timeline (rt2_scene_set_wave_log)
     uint32_t wave_log_n = 0;
@@ -592,17 +579,7 @@ extern "C" void rt2_scene_destroy(rt2_scene* s) {
     (void)hipFree(s->d_host_res);
     (void)hipFree(s->d_host_acc8);
     (void)hipFree(s->d_host_rgb8);
-    (void)hipFree(s->d_query_rays);
-    (void)hipFree(s->d_query_hits);
-    (void)hipFree(s->d_occluded_rays);
-    (void)hipFree(s->d_occluded_out);
-    (void)hipFree(s->d_surface_rays);
-    (void)hipFree(s->d_surface_out);
-    (void)hipFree(s->d_shade_rays);
-    (void)hipFree(s->d_shade_out);
-    (void)hipFree(s->d_radiance_rays);
-    (void)hipFree(s->d_radiance_rng);
-    (void)hipFree(s->d_radiance_out);
+    for (const Staging* b : {&s->stage_rays, &s->stage_rng, &s->stage_out}) (void)hipFree(b->ptr);
     (void)hipFree(s->d_region_ctr);
     if (s->host_stream) (void)hipStreamDestroy(s->host_stream);
     delete s;
@@ -1515,7 +1492,10 @@ extern "C" int rt2_render_linear_host(rt2_scene* s, const rt2_uniforms* u, uint3
 }
 
 /* -------------------------------------------------------------------------
- * Ray queries (rt2_query.h)
+ * Ray queries (rt2_query.h, rt2_occluded.h, rt2_surface.h, rt2_shade.h, rt2_radiance.h)
+ *
+ * The five families share what is below (DESIGN.md "The query frame"): the argument check, the RenderParams fill,
+ * launch_query and the blocking wrappers' staging; each entry point adds its options and its kernels.
  * ----------------------------------------------------------------------- */
 namespace {
 // trace_rays_k5r with the arithmetic of 353 (every group resident) and of 355
@@ -1530,135 +1510,9 @@ constexpr MfmaSpec kQueryResDiag = kt_win(kt_res(false, false, true, 0, true), k
 constexpr MfmaSpec kQueryResYw = kt_yw(kQueryRes);
 constexpr MfmaSpec kQueryResXl = kt_xl(kQueryRes);  // 3 = the exact tests per ray (the render's 400)
 #endif
-constexpr int kQueryBlock = 256;                  // trace_rays_scalar
-constexpr long long kQuerySlice = 1ll << 30;      // rays per trace_rays_scalar launch (its grid: 2^22 blocks)
-// what rt2_scene_diag reports as the variant last launched after a query (renders: a kVariants id, or -1)
-enum : int { Q_RES = -2, Q_RES_L2 = -3, Q_SCALAR = -4, Q_BVH = -5 };
-}  // namespace
+constexpr int kQueryBlock = 256;                  // the *_scalar kernels
+constexpr long long kQuerySlice = 1ll << 30;      // rays per *_scalar launch (its grid: 2^22 blocks)
 
-#ifdef RT2_EXPERIMENTS
-// Not in rt2.h (experiment build): 0 = the product kernel, 1 / 2 / 3 = kQueryResDiag / kQueryResYw / kQueryResXl for
-// scenes of at most kResGroups groups.
-extern "C" int rt2_scene_set_query_arm(rt2_scene* s, int arm) {
-    if (!s || arm < 0 || arm > 3) return -1;
-    s->query_arm = arm;
-    return 0;
-}
-#endif
-
-extern "C" int rt2_trace_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, rt2_hit* d_hits, int flags,
-                              void* stream) {
-    if (!s || n < 0 || (n > 0 && (!d_rays || !d_hits)) || (flags & ~RT2_TRACE_SCALAR) ||
-        (reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 7)) {
-        rt2h::set_error("rt2_trace_rays: bad argument (a scene, n >= 0, rays aligned to 16 B and hits to 8 B, flags "
-                        "0 or RT2_TRACE_SCALAR)");
-        return -1;
-    }
-    if (n == 0) return 0;
-    const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
-    if (bvh && s->n_nodes == 0) {
-        rt2h::set_error("rt2_trace_rays: bad argument (BVH traversal needs the node array)");
-        return -1;
-    }
-    HIPCHECK(hipSetDevice(s->device));
-    hipStream_t st = (hipStream_t)stream;
-    RenderParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.tri = s->d_tri;
-    p.n_tris = s->n_tris;
-    p.mfma_A = s->mfma_A;
-    p.mfma_kt_frag = s->d_mfma_kt;
-    p.nodes = s->d_nodes;
-    p.stack_slots = s->bvh_depth + 2;
-    p.item_counter = s->d_counters;
-    p.seg_counter = s->d_counters + 1;
-    QueryParams q{d_rays, d_hits, (long long)n};
-    // RT2_TRACE_AUTO: the matrix kernel at every ray count.  On config B it beat the scalar kernel in every round
-    // from 2^22 rays down to one 64-ray chunk (36 against 142 us; profiles/trace_rays_ab.json), and below 64 rays
-    // both kernels are one wave whose time no longer falls: no small-batch threshold is needed.
-    const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
-    // a query shares the scene's counters with its renders: the same order
-    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
-    if (matrix) {
-        // one 16-wave workgroup per CU, and no more workgroups than have 1,024 rays each:
-        // every one of them brings the resident records into its LDS
-        const unsigned blocks = (unsigned)std::min<long long>(s->num_cus, (n + 1023) / 1024);
-        const bool resident = (s->n_tris + 31) / 32 <= kResGroups;
-#ifdef RT2_EXPERIMENTS
-        if (resident && s->query_arm == 1)
-            hipLaunchKernelGGL(trace_rays_k5r<kQueryResDiag>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
-        else if (resident && s->query_arm == 2)
-            hipLaunchKernelGGL(trace_rays_k5r<kQueryResYw>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
-        else if (resident && s->query_arm == 3)
-            hipLaunchKernelGGL(trace_rays_k5r<kQueryResXl>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
-        else
-#endif
-        if (resident)
-            hipLaunchKernelGGL(trace_rays_k5r<kQueryRes>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
-        else
-            hipLaunchKernelGGL(trace_rays_k5r<kQueryResL2>, dim3(blocks), dim3(kQueryResL2.block), 0, st, p, q);
-        HIPCHECK(hipGetLastError());
-        s->last_kind = K_MFMA;
-        s->last_variant = resident ? Q_RES : Q_RES_L2;
-    } else {
-        for (long long i0 = 0; i0 < (long long)n; i0 += kQuerySlice) {
-            q.rays = d_rays + i0;
-            q.hits = d_hits + i0;
-            q.n = std::min<long long>(kQuerySlice, (long long)n - i0);
-            const unsigned blocks = (unsigned)((q.n + kQueryBlock - 1) / kQueryBlock);
-            if (bvh)
-                hipLaunchKernelGGL((trace_rays_scalar<kQueryBlock, true>), dim3(blocks), dim3(kQueryBlock),
-                                   (size_t)p.stack_slots * kQueryBlock * sizeof(int), st, p, q);
-            else
-                hipLaunchKernelGGL((trace_rays_scalar<kQueryBlock, false>), dim3(blocks), dim3(kQueryBlock), 0, st, p,
-                                   q);
-            HIPCHECK(hipGetLastError());
-        }
-        s->last_kind = bvh ? K_BVH : K_SMEM;
-        s->last_variant = bvh ? Q_BVH : Q_SCALAR;
-    }
-    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(s->last_launch, st));
-    s->last_launch_valid = true;
-    s->tests_per_seg = (unsigned long long)s->n_tris;
-    return 0;
-}
-
-extern "C" int rt2_trace_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n, rt2_hit* hits, int flags) {
-    if (!s || n < 0 || (n > 0 && (!rays || !hits)) || (flags & ~RT2_TRACE_SCALAR)) {
-        rt2h::set_error("rt2_trace_rays_host: bad argument (a scene, n >= 0, flags 0 or RT2_TRACE_SCALAR)");
-        return -1;
-    }
-    if (n == 0) return 0;
-    if (s->traversal == RT2_TRAVERSAL_BVH && s->n_nodes == 0) {
-        rt2h::set_error("rt2_trace_rays_host: bad argument (BVH traversal needs the node array)");
-        return -1;
-    }
-    HIPCHECK(hipSetDevice(s->device));
-    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
-    hipStream_t st = s->host_stream;
-    if ((size_t)n > s->query_cap) {
-        HIPCHECK(hipStreamSynchronize(st));
-        (void)hipFree(s->d_query_rays);
-        (void)hipFree(s->d_query_hits);
-        s->d_query_rays = nullptr;
-        s->d_query_hits = nullptr;
-        s->query_cap = 0;
-        HIPCHECK(hipMalloc(&s->d_query_rays, (size_t)n * sizeof(rt2_ray)));
-        HIPCHECK(hipMalloc(&s->d_query_hits, (size_t)n * sizeof(rt2_hit)));
-        s->query_cap = (size_t)n;
-    }
-    HIPCHECK(hipMemcpyAsync(s->d_query_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
-    if (rt2_trace_rays(s, s->d_query_rays, n, s->d_query_hits, flags, st) != 0) return -1;
-    HIPCHECK(hipMemcpyAsync(hits, s->d_query_hits, (size_t)n * sizeof(rt2_hit), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    return 0;
-}
-
-/* -------------------------------------------------------------------------
- * Occlusion queries (rt2_occluded.h)
- * ----------------------------------------------------------------------- */
-namespace {
 // occluded_k5r: trace_rays_k5r's frame, windows of `win` groups, no Y product (y = false: a frame whose resident
 // form leaves the T1 records out of LDS) or the Y product
 // from the second window on; wave = the episode per wave (any_window_wave) instead of per ray
@@ -1672,16 +1526,190 @@ constexpr bool kOccY = false;
 constexpr bool kOccWave = true;
 constexpr OccSpec kOccRes = occ_spec(false, kOccWin, kOccY, kOccWave);
 constexpr OccSpec kOccResL2 = occ_spec(true, kOccWin, kOccY, kOccWave);
-// after kQuery's codes: what rt2_scene_diag reports as the variant last launched
-enum : int { O_RES = -6, O_RES_L2 = -7, O_SCALAR = -8, O_BVH = -9 };
+static_assert(kQueryRes.block == kQueryResL2.block && kOccRes.m.block == kQueryRes.block, "one block size");
 
-template <OccSpec O>
-void launch_occluded_k5r(unsigned blocks, hipStream_t st, const RenderParams& p, const OccParams& q) {
-    hipLaunchKernelGGL(occluded_k5r<O>, dim3(blocks), dim3(O.m.block), 0, st, p, q);
+// What rt2_scene_diag reports as the variant last launched after a query (renders: a kVariants id, or -1):
+// -2 .. -21, four forms per family.
+enum QueryFamily : int { QF_CLOSEST, QF_OCCLUDED, QF_SURFACE, QF_SHADE, QF_RADIANCE };
+enum QueryForm : int { QV_RES, QV_RES_L2, QV_SCALAR, QV_BVH };
+constexpr int query_code(QueryFamily f, QueryForm v) { return -2 - 4 * f - v; }
+static_assert(query_code(QF_CLOSEST, QV_RES) == -2 && query_code(QF_RADIANCE, QV_BVH) == -21, "rt2/__init__.py");
+
+// One array argument of a ray query: device pointers are aligned to `align` bytes.
+struct QueryArray {
+    const char* name;
+    const void* ptr;
+    unsigned align;
+};
+
+// The argument check of the five ray-array families, before any device call and before the scene is read for
+// n = 0.  `device`: the arrays' alignment too.
+int query_args(const char* who, const rt2_scene* s, int64_t n, int flags, bool device,
+               std::initializer_list<QueryArray> arrays) {
+    bool bad = !s || n < 0 || (flags & ~RT2_TRACE_SCALAR);
+    std::string need;
+    for (const QueryArray& a : arrays) {
+        bad = bad || (n > 0 && !a.ptr) || (device && (reinterpret_cast<uintptr_t>(a.ptr) & (a.align - 1)));
+        need += std::string(", ") + a.name + (device && a.align > 1 ? " aligned to " + std::to_string(a.align) + " B" : "");
+    }
+    if (bad) {
+        rt2h::set_error(std::string(who) + ": bad argument (a scene, n >= 0" + need + ", flags 0 or RT2_TRACE_SCALAR)");
+        return -1;
+    }
+    if (n > 0 && s->traversal == RT2_TRAVERSAL_BVH && s->n_nodes == 0) {
+        rt2h::set_error(std::string(who) + ": bad argument (BVH traversal needs the node array)");
+        return -1;
+    }
+    return 0;
+}
+
+// What every query's search reads.
+RenderParams query_params(const rt2_scene* s) {
+    RenderParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.tri = s->d_tri;
+    p.n_tris = s->n_tris;
+    p.mfma_A = s->mfma_A;
+    p.mfma_kt_frag = s->d_mfma_kt;
+    p.nodes = s->d_nodes;
+    p.stack_slots = s->bvh_depth + 2;
+    p.item_counter = s->d_counters;
+    p.seg_counter = s->d_counters + 1;
+    return p;
+}
+
+// ... and what surface_record, shade_step and radiance_step read of the materials and textures.
+void query_shading_params(const rt2_scene* s, RenderParams& p) {
+    p.unit_n = s->d_unit_n;
+    p.tri_mtl = s->d_mtl;
+    p.mats = s->d_mats;
+    p.n_mats = s->n_mats;
+    p.raw = s->d_raw;
+    p.texels = s->d_texels;
+    p.tex_desc = s->d_tex_desc;
+    p.n_tex = s->n_tex;
+    p.num_textures = std::min(s->n_tex, 5);  // a ray query has no uniforms: the images bound, at most the five units
+}
+
+// A family's resident or L2 kernel on `blocks` workgroups, and its scalar kernel on the rays of q.
+template <auto RES, auto RES_L2, class Q>
+void launch_k5r(bool resident, unsigned blocks, hipStream_t st, const RenderParams& p, const Q& q) {
+    if (resident)
+        hipLaunchKernelGGL(RES, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
+    else
+        hipLaunchKernelGGL(RES_L2, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
+}
+template <auto ARRAY, auto BVH, class Q>
+void launch_scalar(bool bvh, hipStream_t st, const RenderParams& p, const Q& q) {
+    const unsigned blocks = (unsigned)((q.n + kQueryBlock - 1) / kQueryBlock);
+    if (bvh)  // closest_bvh's stack
+        hipLaunchKernelGGL(BVH, dim3(blocks), dim3(kQueryBlock), (size_t)p.stack_slots * kQueryBlock * sizeof(int), st,
+                           p, q);
+    else
+        hipLaunchKernelGGL(ARRAY, dim3(blocks), dim3(kQueryBlock), 0, st, p, q);
+}
+
+// Launches one query of n > 0 rays on st.  matrix_k(resident, blocks) launches the family's matrix kernel,
+// scalar_k(bvh, i0, count) its scalar kernel for the rays [i0, i0 + count).
+// RT2_TRACE_AUTO: the matrix kernel at every ray count.  On config B it beat the scalar kernel in every round
+// from 2^22 rays down to one 64-ray chunk (closest hit: 36 against 142 us, profiles/trace_rays_ab.json; preview
+// shading with the shadow ray: 0.83 against 4.99 ms at 2^22, 52 against 289 us at 64, profiles/shade_ab.json), and
+// below 64 rays both kernels are one wave whose time no longer falls: no small-batch threshold is needed.
+template <class Matrix, class Scalar>
+int launch_query(rt2_scene* s, QueryFamily family, int64_t n, int flags, hipStream_t st, Matrix matrix_k,
+                 Scalar scalar_k) {
+    const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
+    const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
+    // a query shares the scene's counters with its renders: the same order
+    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
+    QueryForm form;
+    if (matrix) {
+        // one 16-wave workgroup per CU, and no more workgroups than have 1,024 rays each:
+        // every one of them brings the resident records into its LDS
+        const unsigned blocks = (unsigned)std::min<long long>(s->num_cus, (n + 1023) / 1024);
+        const bool resident = (s->n_tris + 31) / 32 <= kResGroups;
+        matrix_k(resident, blocks);
+        HIPCHECK(hipGetLastError());
+        form = resident ? QV_RES : QV_RES_L2;
+    } else {
+        for (long long i0 = 0; i0 < (long long)n; i0 += kQuerySlice) {
+            scalar_k(bvh, i0, std::min<long long>(kQuerySlice, (long long)n - i0));
+            HIPCHECK(hipGetLastError());
+        }
+        form = bvh ? QV_BVH : QV_SCALAR;
+    }
+    s->last_kind = matrix ? K_MFMA : bvh ? K_BVH : K_SMEM;
+    s->last_variant = query_code(family, form);
+    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(s->last_launch, st));
+    s->last_launch_valid = true;
+    s->tests_per_seg = (unsigned long long)s->n_tris;
+    return 0;
+}
+
+// Grows one of the scene's staging buffers to `bytes` (the stream is drained first: the old buffer may still be
+// in use).
+int staging_grow(rt2_scene* s, Staging& b, size_t bytes) {
+    if (bytes <= b.cap) return 0;
+    HIPCHECK(hipStreamSynchronize(s->host_stream));
+    (void)hipFree(b.ptr);
+    b.ptr = nullptr;
+    b.cap = 0;
+    HIPCHECK(hipMalloc(&b.ptr, bytes));
+    b.cap = bytes;
+    return 0;
+}
+
+// The blocking wrappers' start: the scene's device, host_stream, and staging for n rays, n stream words when
+// `rng`, and out_bytes of results.
+int staging_begin(rt2_scene* s, size_t n, bool rng, size_t out_bytes) {
+    HIPCHECK(hipSetDevice(s->device));
+    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    if (staging_grow(s, s->stage_rays, n * sizeof(rt2_ray)) != 0) return -1;
+    if (rng && staging_grow(s, s->stage_rng, n * sizeof(uint32_t)) != 0) return -1;
+    return staging_grow(s, s->stage_out, out_bytes);
+}
+
+// A blocking ray-array query over host arrays: rays (and the streams, when rng) in, query(d_rays, d_rng, d_out,
+// stream), the records (and the streams) out.
+template <class Out, class Query>
+int query_host(rt2_scene* s, const rt2_ray* rays, int64_t n, uint32_t* rng, Out* out, Query query) {
+    if (staging_begin(s, (size_t)n, rng != nullptr, (size_t)n * sizeof(Out)) != 0) return -1;
+    hipStream_t st = s->host_stream;
+    rt2_ray* d_rays = static_cast<rt2_ray*>(s->stage_rays.ptr);
+    uint32_t* d_rng = static_cast<uint32_t*>(s->stage_rng.ptr);
+    Out* d_out = static_cast<Out*>(s->stage_out.ptr);
+    HIPCHECK(hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
+    if (rng) HIPCHECK(hipMemcpyAsync(d_rng, rng, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (query(d_rays, d_rng, d_out, st) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(Out), hipMemcpyDeviceToHost, st));
+    if (rng) HIPCHECK(hipMemcpyAsync(rng, d_rng, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// The option checks of both shading and both radiance entry points (whatever n).
+int shade_opts_args(const char* who, const rt2_shade_opts* o) {
+    if (o && !o->pad[0] && !o->pad[1] && !o->pad[2] && o->max_bounce >= 1 && o->max_bounce <= 256) return 0;
+    rt2h::set_error(std::string(who) + ": bad argument (options with pad 0 and max_bounce in 1 .. 256)");
+    return -1;
+}
+int path_opts_args(const char* who, const rt2_path_opts* o) {
+    if (o && !o->pad[0] && !o->pad[1] && o->max_bounce >= 1 && o->max_bounce <= 256) return 0;
+    rt2h::set_error(std::string(who) + ": bad argument (options with pad 0 and max_bounce in 1 .. 256)");
+    return -1;
 }
 }  // namespace
 
 #ifdef RT2_EXPERIMENTS
+// Not in rt2.h (experiment build): 0 = the product kernel, 1 / 2 / 3 = kQueryResDiag / kQueryResYw / kQueryResXl for
+// scenes of at most kResGroups groups.
+extern "C" int rt2_scene_set_query_arm(rt2_scene* s, int arm) {
+    if (!s || arm < 0 || arm > 3) return -1;
+    s->query_arm = arm;
+    return 0;
+}
+
 // Not in rt2.h (experiment build): the A/B arms of occluded_k5r, for the resident and the L2 form alike.  0 = the
 // product kernel; 1 = a window of kResWin without Y (no exit inside the resident stretch: the control); 2, 3 =
 // windows of 12 and 6 groups without Y; 4, 5 = those windows with the Y product from the second window on; 6 = a
@@ -1694,250 +1722,201 @@ extern "C" int rt2_scene_set_occluded_arm(rt2_scene* s, int arm) {
 }
 #endif
 
-extern "C" int rt2_occluded(rt2_scene* s, const rt2_ray* d_rays, int64_t n, uint8_t* d_occluded, int flags,
-                            void* stream) {
-    if (!s || n < 0 || (n > 0 && (!d_rays || !d_occluded)) || (flags & ~RT2_TRACE_SCALAR) ||
-        (reinterpret_cast<uintptr_t>(d_rays) & 15)) {
-        rt2h::set_error("rt2_occluded: bad argument (a scene, n >= 0, rays aligned to 16 B, flags 0 or "
-                        "RT2_TRACE_SCALAR)");
-        return -1;
-    }
+extern "C" int rt2_trace_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, rt2_hit* d_hits, int flags,
+                              void* stream) {
+    if (query_args("rt2_trace_rays", s, n, flags, true, {{"rays", d_rays, 16}, {"hits", d_hits, 8}}) != 0) return -1;
     if (n == 0) return 0;
-    const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
-    if (bvh && s->n_nodes == 0) {
-        rt2h::set_error("rt2_occluded: bad argument (BVH traversal needs the node array)");
-        return -1;
-    }
     HIPCHECK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    RenderParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.tri = s->d_tri;
-    p.n_tris = s->n_tris;
-    p.mfma_A = s->mfma_A;
-    p.mfma_kt_frag = s->d_mfma_kt;
-    p.nodes = s->d_nodes;
-    p.stack_slots = s->bvh_depth + 2;
-    p.item_counter = s->d_counters;
-    p.seg_counter = s->d_counters + 1;
-    OccParams q{d_rays, d_occluded, (long long)n};
-    // the kernel choice of rt2_trace_rays
-    const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
-    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
-    if (matrix) {
-        const unsigned blocks = (unsigned)std::min<long long>(s->num_cus, (n + 1023) / 1024);
-        const bool resident = (s->n_tris + 31) / 32 <= kResGroups;
-        int arm = 0;
+    const RenderParams p = query_params(s);
+    const QueryParams q{d_rays, d_hits, (long long)n};
+    return launch_query(
+        s, QF_CLOSEST, n, flags, st,
+        [&](bool resident, unsigned blocks) {
+            constexpr auto l2 = trace_rays_k5r<kQueryResL2>;
 #ifdef RT2_EXPERIMENTS
-        arm = s->occluded_arm;
+            switch (s->query_arm) {  // the arms replace the resident kernel only
+            case 1: return launch_k5r<trace_rays_k5r<kQueryResDiag>, l2>(resident, blocks, st, p, q);
+            case 2: return launch_k5r<trace_rays_k5r<kQueryResYw>, l2>(resident, blocks, st, p, q);
+            case 3: return launch_k5r<trace_rays_k5r<kQueryResXl>, l2>(resident, blocks, st, p, q);
+            }
 #endif
-        auto go = [&](auto res, auto l2) {
-            if (resident)
-                launch_occluded_k5r<decltype(res)::value>(blocks, st, p, q);
-            else
-                launch_occluded_k5r<decltype(l2)::value>(blocks, st, p, q);
-        };
-        switch (arm) {
+            launch_k5r<trace_rays_k5r<kQueryRes>, l2>(resident, blocks, st, p, q);
+        },
+        [&](bool bvh, long long i0, long long count) {
+            launch_scalar<trace_rays_scalar<kQueryBlock, false>, trace_rays_scalar<kQueryBlock, true>>(
+                bvh, st, p, QueryParams{d_rays + i0, d_hits + i0, count});
+        });
+}
+
+extern "C" int rt2_trace_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n, rt2_hit* hits, int flags) {
+    if (query_args("rt2_trace_rays_host", s, n, flags, false, {{"rays", rays, 16}, {"hits", hits, 8}}) != 0) return -1;
+    if (n == 0) return 0;
+    return query_host(s, rays, n, nullptr, hits, [&](const rt2_ray* d_rays, uint32_t*, rt2_hit* d_hits, hipStream_t st) {
+        return rt2_trace_rays(s, d_rays, n, d_hits, flags, st);
+    });
+}
+
+extern "C" int rt2_occluded(rt2_scene* s, const rt2_ray* d_rays, int64_t n, uint8_t* d_occluded, int flags,
+                            void* stream) {
+    if (query_args("rt2_occluded", s, n, flags, true, {{"rays", d_rays, 16}, {"occluded", d_occluded, 1}}) != 0)
+        return -1;
+    if (n == 0) return 0;
+    HIPCHECK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    const RenderParams p = query_params(s);
+    const OccParams q{d_rays, d_occluded, (long long)n};
+    return launch_query(
+        s, QF_OCCLUDED, n, flags, st,
+        [&](bool resident, unsigned blocks) {
 #ifdef RT2_EXPERIMENTS
-#define RT2_OCC_ARM(A, W, Y, V)                                                                       \
-    case A:                                                                                           \
-        go(std::integral_constant<OccSpec, occ_spec(false, W, Y, V)>{},                               \
-           std::integral_constant<OccSpec, occ_spec(true, W, Y, V)>{});                               \
-        break;
-            RT2_OCC_ARM(1, kResWin, false, false)
-            RT2_OCC_ARM(2, 12, false, false)
-            RT2_OCC_ARM(3, 6, false, false)
-            RT2_OCC_ARM(4, 12, true, false)
-            RT2_OCC_ARM(5, 6, true, false)
-            RT2_OCC_ARM(6, 3, false, false)
-            RT2_OCC_ARM(7, kResWin, false, true)
-            RT2_OCC_ARM(8, 12, false, true)
-            RT2_OCC_ARM(9, 6, false, true)
-            RT2_OCC_ARM(10, 3, false, true)
+            switch (s->occluded_arm) {
+#define RT2_OCC_ARM(A, W, Y, V)                                                                             \
+    case A:                                                                                                 \
+        return launch_k5r<occluded_k5r<occ_spec(false, W, Y, V)>, occluded_k5r<occ_spec(true, W, Y, V)>>( \
+            resident, blocks, st, p, q);
+                RT2_OCC_ARM(1, kResWin, false, false)
+                RT2_OCC_ARM(2, 12, false, false)
+                RT2_OCC_ARM(3, 6, false, false)
+                RT2_OCC_ARM(4, 12, true, false)
+                RT2_OCC_ARM(5, 6, true, false)
+                RT2_OCC_ARM(6, 3, false, false)
+                RT2_OCC_ARM(7, kResWin, false, true)
+                RT2_OCC_ARM(8, 12, false, true)
+                RT2_OCC_ARM(9, 6, false, true)
+                RT2_OCC_ARM(10, 3, false, true)
 #undef RT2_OCC_ARM
+            }
 #endif
-        default:
-            go(std::integral_constant<OccSpec, kOccRes>{}, std::integral_constant<OccSpec, kOccResL2>{});
-        }
-        HIPCHECK(hipGetLastError());
-        s->last_kind = K_MFMA;
-        s->last_variant = resident ? O_RES : O_RES_L2;
-    } else {
-        for (long long i0 = 0; i0 < (long long)n; i0 += kQuerySlice) {
-            q.rays = d_rays + i0;
-            q.out = d_occluded + i0;
-            q.n = std::min<long long>(kQuerySlice, (long long)n - i0);
-            const unsigned blocks = (unsigned)((q.n + kQueryBlock - 1) / kQueryBlock);
-            if (bvh)
-                hipLaunchKernelGGL((occluded_scalar<kQueryBlock, true>), dim3(blocks), dim3(kQueryBlock),
-                                   (size_t)p.stack_slots * kQueryBlock * sizeof(int), st, p, q);
-            else
-                hipLaunchKernelGGL((occluded_scalar<kQueryBlock, false>), dim3(blocks), dim3(kQueryBlock), 0, st, p,
-                                   q);
-            HIPCHECK(hipGetLastError());
-        }
-        s->last_kind = bvh ? K_BVH : K_SMEM;
-        s->last_variant = bvh ? O_BVH : O_SCALAR;
-    }
-    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(s->last_launch, st));
-    s->last_launch_valid = true;
-    s->tests_per_seg = (unsigned long long)s->n_tris;
-    return 0;
+            launch_k5r<occluded_k5r<kOccRes>, occluded_k5r<kOccResL2>>(resident, blocks, st, p, q);
+        },
+        [&](bool bvh, long long i0, long long count) {
+            launch_scalar<occluded_scalar<kQueryBlock, false>, occluded_scalar<kQueryBlock, true>>(
+                bvh, st, p, OccParams{d_rays + i0, d_occluded + i0, count});
+        });
 }
 
 extern "C" int rt2_occluded_host(rt2_scene* s, const rt2_ray* rays, int64_t n, uint8_t* occluded, int flags) {
-    if (!s || n < 0 || (n > 0 && (!rays || !occluded)) || (flags & ~RT2_TRACE_SCALAR)) {
-        rt2h::set_error("rt2_occluded_host: bad argument (a scene, n >= 0, flags 0 or RT2_TRACE_SCALAR)");
+    if (query_args("rt2_occluded_host", s, n, flags, false, {{"rays", rays, 16}, {"occluded", occluded, 1}}) != 0)
         return -1;
-    }
     if (n == 0) return 0;
-    if (s->traversal == RT2_TRAVERSAL_BVH && s->n_nodes == 0) {
-        rt2h::set_error("rt2_occluded_host: bad argument (BVH traversal needs the node array)");
-        return -1;
-    }
-    HIPCHECK(hipSetDevice(s->device));
-    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
-    hipStream_t st = s->host_stream;
-    if ((size_t)n > s->occluded_cap) {
-        HIPCHECK(hipStreamSynchronize(st));
-        (void)hipFree(s->d_occluded_rays);
-        (void)hipFree(s->d_occluded_out);
-        s->d_occluded_rays = nullptr;
-        s->d_occluded_out = nullptr;
-        s->occluded_cap = 0;
-        HIPCHECK(hipMalloc(&s->d_occluded_rays, (size_t)n * sizeof(rt2_ray)));
-        HIPCHECK(hipMalloc(&s->d_occluded_out, (size_t)n));
-        s->occluded_cap = (size_t)n;
-    }
-    HIPCHECK(hipMemcpyAsync(s->d_occluded_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
-    if (rt2_occluded(s, s->d_occluded_rays, n, s->d_occluded_out, flags, st) != 0) return -1;
-    HIPCHECK(hipMemcpyAsync(occluded, s->d_occluded_out, (size_t)n, hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    return 0;
+    return query_host(s, rays, n, nullptr, occluded, [&](const rt2_ray* d_rays, uint32_t*, uint8_t* d_out, hipStream_t st) {
+        return rt2_occluded(s, d_rays, n, d_out, flags, st);
+    });
 }
-
-/* -------------------------------------------------------------------------
- * Surface queries (rt2_surface.h)
- * ----------------------------------------------------------------------- */
-namespace {
-// after the occlusion queries' codes: what rt2_scene_diag reports as the variant last launched
-enum : int { S_RES = -10, S_RES_L2 = -11, S_SCALAR = -12, S_BVH = -13 };
-
-// Grows one of the scene's two surface staging buffers to n records (the stream is drained first: the old
-// buffer may still be in use).
-template <class T>
-int surface_staging(rt2_scene* s, T*& buf, size_t& cap, size_t n) {
-    if (n <= cap) return 0;
-    HIPCHECK(hipStreamSynchronize(s->host_stream));
-    (void)hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-    HIPCHECK(hipMalloc(&buf, n * sizeof(T)));
-    cap = n;
-    return 0;
-}
-}  // namespace
 
 extern "C" int rt2_surface_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, rt2_surface* d_out, int flags,
                                 void* stream) {
-    if (!s || n < 0 || (n > 0 && (!d_rays || !d_out)) || (flags & ~RT2_TRACE_SCALAR) ||
-        (reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15)) {
-        rt2h::set_error("rt2_surface_rays: bad argument (a scene, n >= 0, rays and records aligned to 16 B, flags 0 "
-                        "or RT2_TRACE_SCALAR)");
+    if (query_args("rt2_surface_rays", s, n, flags, true, {{"rays", d_rays, 16}, {"records", d_out, 16}}) != 0)
         return -1;
-    }
     if (n == 0) return 0;
-    const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
-    if (bvh && s->n_nodes == 0) {
-        rt2h::set_error("rt2_surface_rays: bad argument (BVH traversal needs the node array)");
-        return -1;
-    }
     HIPCHECK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    RenderParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.tri = s->d_tri;
-    p.n_tris = s->n_tris;
-    p.mfma_A = s->mfma_A;
-    p.mfma_kt_frag = s->d_mfma_kt;
-    p.nodes = s->d_nodes;
-    p.stack_slots = s->bvh_depth + 2;
-    p.item_counter = s->d_counters;
-    p.seg_counter = s->d_counters + 1;
-    // what surface_record reads
-    p.unit_n = s->d_unit_n;
-    p.tri_mtl = s->d_mtl;
-    p.mats = s->d_mats;
-    p.n_mats = s->n_mats;
-    p.raw = s->d_raw;
-    p.texels = s->d_texels;
-    p.tex_desc = s->d_tex_desc;
-    p.n_tex = s->n_tex;
-    p.num_textures = std::min(s->n_tex, 5);  // a ray query has no uniforms: the images bound, at most the five units
-    SurfaceParams q{d_rays, d_out, (long long)n};
-    // the kernel choice of rt2_trace_rays
-    const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
-    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
-    if (matrix) {
-        const unsigned blocks = (unsigned)std::min<long long>(s->num_cus, (n + 1023) / 1024);
-        const bool resident = (s->n_tris + 31) / 32 <= kResGroups;
-        if (resident)
-            hipLaunchKernelGGL(surface_k5r<kQueryRes>, dim3(blocks), dim3(kQueryRes.block), 0, st, p, q);
-        else
-            hipLaunchKernelGGL(surface_k5r<kQueryResL2>, dim3(blocks), dim3(kQueryResL2.block), 0, st, p, q);
-        HIPCHECK(hipGetLastError());
-        s->last_kind = K_MFMA;
-        s->last_variant = resident ? S_RES : S_RES_L2;
-    } else {
-        for (long long i0 = 0; i0 < (long long)n; i0 += kQuerySlice) {
-            q.rays = d_rays + i0;
-            q.out = d_out + i0;
-            q.n = std::min<long long>(kQuerySlice, (long long)n - i0);
-            const unsigned blocks = (unsigned)((q.n + kQueryBlock - 1) / kQueryBlock);
-            if (bvh)
-                hipLaunchKernelGGL((surface_scalar<kQueryBlock, true>), dim3(blocks), dim3(kQueryBlock),
-                                   (size_t)p.stack_slots * kQueryBlock * sizeof(int), st, p, q);
-            else
-                hipLaunchKernelGGL((surface_scalar<kQueryBlock, false>), dim3(blocks), dim3(kQueryBlock), 0, st, p,
-                                   q);
-            HIPCHECK(hipGetLastError());
-        }
-        s->last_kind = bvh ? K_BVH : K_SMEM;
-        s->last_variant = bvh ? S_BVH : S_SCALAR;
-    }
-    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(s->last_launch, st));
-    s->last_launch_valid = true;
-    s->tests_per_seg = (unsigned long long)s->n_tris;
-    return 0;
+    RenderParams p = query_params(s);
+    query_shading_params(s, p);
+    const SurfaceParams q{d_rays, d_out, (long long)n};
+    return launch_query(
+        s, QF_SURFACE, n, flags, st,
+        [&](bool resident, unsigned blocks) {
+            launch_k5r<surface_k5r<kQueryRes>, surface_k5r<kQueryResL2>>(resident, blocks, st, p, q);
+        },
+        [&](bool bvh, long long i0, long long count) {
+            launch_scalar<surface_scalar<kQueryBlock, false>, surface_scalar<kQueryBlock, true>>(
+                bvh, st, p, SurfaceParams{d_rays + i0, d_out + i0, count});
+        });
 }
 
 extern "C" int rt2_surface_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n, rt2_surface* out, int flags) {
-    if (!s || n < 0 || (n > 0 && (!rays || !out)) || (flags & ~RT2_TRACE_SCALAR)) {
-        rt2h::set_error("rt2_surface_rays_host: bad argument (a scene, n >= 0, flags 0 or RT2_TRACE_SCALAR)");
+    if (query_args("rt2_surface_rays_host", s, n, flags, false, {{"rays", rays, 16}, {"records", out, 16}}) != 0)
         return -1;
-    }
     if (n == 0) return 0;
-    if (s->traversal == RT2_TRAVERSAL_BVH && s->n_nodes == 0) {
-        rt2h::set_error("rt2_surface_rays_host: bad argument (BVH traversal needs the node array)");
-        return -1;
-    }
-    HIPCHECK(hipSetDevice(s->device));
-    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
-    hipStream_t st = s->host_stream;
-    if (surface_staging(s, s->d_surface_rays, s->surface_rays_cap, (size_t)n) != 0) return -1;
-    if (surface_staging(s, s->d_surface_out, s->surface_out_cap, (size_t)n) != 0) return -1;
-    HIPCHECK(hipMemcpyAsync(s->d_surface_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
-    if (rt2_surface_rays(s, s->d_surface_rays, n, s->d_surface_out, flags, st) != 0) return -1;
-    HIPCHECK(hipMemcpyAsync(out, s->d_surface_out, (size_t)n * sizeof(rt2_surface), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    return 0;
+    return query_host(s, rays, n, nullptr, out, [&](const rt2_ray* d_rays, uint32_t*, rt2_surface* d_out, hipStream_t st) {
+        return rt2_surface_rays(s, d_rays, n, d_out, flags, st);
+    });
 }
 
+extern "C" int rt2_shade_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, const rt2_shade_opts* opts,
+                              rt2_shaded* d_out, int flags, void* stream) {
+    const char* who = "rt2_shade_rays";
+    if (query_args(who, s, n, flags, true, {{"rays", d_rays, 16}, {"records", d_out, 16}}) != 0) return -1;
+    if (shade_opts_args(who, opts) != 0) return -1;
+    if (n == 0) return 0;
+    HIPCHECK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    RenderParams p = query_params(s);
+    query_shading_params(s, p);
+    p.maxBounce = opts->max_bounce;
+    p.basicShadow = opts->shadow;
+    p.light[0] = opts->light[0];
+    p.light[1] = opts->light[1];
+    p.light[2] = opts->light[2];
+    const ShadeParams q{d_rays, d_out, (long long)n};
+    return launch_query(
+        s, QF_SHADE, n, flags, st,
+        [&](bool resident, unsigned blocks) {
+            launch_k5r<shade_rays_k5r<kOccRes>, shade_rays_k5r<kOccResL2>>(resident, blocks, st, p, q);
+        },
+        [&](bool bvh, long long i0, long long count) {
+            launch_scalar<shade_rays_scalar<kQueryBlock, false>, shade_rays_scalar<kQueryBlock, true>>(
+                bvh, st, p, ShadeParams{d_rays + i0, d_out + i0, count});
+        });
+}
+
+extern "C" int rt2_shade_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n, const rt2_shade_opts* opts,
+                                   rt2_shaded* out, int flags) {
+    const char* who = "rt2_shade_rays_host";
+    if (query_args(who, s, n, flags, false, {{"rays", rays, 16}, {"records", out, 16}}) != 0) return -1;
+    if (shade_opts_args(who, opts) != 0) return -1;
+    if (n == 0) return 0;
+    return query_host(s, rays, n, nullptr, out, [&](const rt2_ray* d_rays, uint32_t*, rt2_shaded* d_out, hipStream_t st) {
+        return rt2_shade_rays(s, d_rays, n, opts, d_out, flags, st);
+    });
+}
+
+extern "C" int rt2_radiance_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, const rt2_path_opts* opts,
+                                 uint32_t* d_rng, rt2_radiance* d_out, int flags, void* stream) {
+    const char* who = "rt2_radiance_rays";
+    if (query_args(who, s, n, flags, true, {{"rays", d_rays, 16}, {"rng", d_rng, 4}, {"records", d_out, 16}}) != 0)
+        return -1;
+    if (path_opts_args(who, opts) != 0) return -1;
+    if (n == 0) return 0;
+    HIPCHECK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    RenderParams p = query_params(s);
+    query_shading_params(s, p);
+    p.maxBounce = opts->max_bounce;
+    p.envLight = opts->environmental_light;
+    const RadianceParams q{d_rays, d_rng, d_out, (long long)n};
+    return launch_query(
+        s, QF_RADIANCE, n, flags, st,
+        [&](bool resident, unsigned blocks) {
+            launch_k5r<radiance_rays_k5r<kOccRes>, radiance_rays_k5r<kOccResL2>>(resident, blocks, st, p, q);
+        },
+        [&](bool bvh, long long i0, long long count) {
+            launch_scalar<radiance_rays_scalar<kQueryBlock, false>, radiance_rays_scalar<kQueryBlock, true>>(
+                bvh, st, p, RadianceParams{d_rays + i0, d_rng + i0, d_out + i0, count});
+        });
+}
+
+extern "C" int rt2_radiance_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n, const rt2_path_opts* opts,
+                                      uint32_t* rng, rt2_radiance* out, int flags) {
+    const char* who = "rt2_radiance_rays_host";
+    if (query_args(who, s, n, flags, false, {{"rays", rays, 16}, {"rng", rng, 4}, {"records", out, 16}}) != 0)
+        return -1;
+    if (path_opts_args(who, opts) != 0) return -1;
+    if (n == 0) return 0;
+    return query_host(s, rays, n, rng, out, [&](const rt2_ray* d_rays, uint32_t* d_rng, rt2_radiance* d_out, hipStream_t st) {
+        return rt2_radiance_rays(s, d_rays, n, opts, d_rng, d_out, flags, st);
+    });
+}
+
+/* -------------------------------------------------------------------------
+ * Ray generators: the preview camera (rt2_surface.h) and the path tracer's (rt2_radiance.h)
+ * ----------------------------------------------------------------------- */
+namespace {
 // The argument checks of both camera-ray entry points; the slab's pixel count in *n.
-static int camera_rays_args(const char* who, const rt2_scene* s, const rt2_uniforms* u, rt2_shard sh,
-                            const void* rays, bool device, long long* n) {
+int camera_rays_args(const char* who, const rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, const void* rays,
+                     bool device, long long* n) {
     const std::string w(who);
     if (!s || !u) {
         rt2h::set_error(w + ": bad argument (a scene and uniforms)");
@@ -1960,191 +1939,6 @@ static int camera_rays_args(const char* who, const rt2_scene* s, const rt2_unifo
     return 0;
 }
 
-extern "C" int rt2_camera_rays(rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, rt2_ray* d_rays, void* stream) {
-    long long n = 0;
-    if (camera_rays_args("rt2_camera_rays", s, u, sh, d_rays, true, &n) != 0) return -1;
-    if (n == 0) return 0;
-    HIPCHECK(hipSetDevice(s->device));
-    CameraParams c;
-    std::memset(&c, 0, sizeof(c));
-    auto cp = [](float* d, const rt2_vec4& v) {
-        d[0] = v.x;
-        d[1] = v.y;
-        d[2] = v.z;
-    };
-    cp(c.cam, u->cameraPos);
-    cp(c.vpRight, u->viewportRight);
-    cp(c.vpUp, u->viewportUp);
-    cp(c.vpFront, u->viewportFront);
-    c.W = (int)u->width;
-    c.H = (int)u->height;
-    c.tile_rows = sh.tile_rows;
-    c.rank = sh.rank;
-    c.nranks = sh.nranks;
-    c.n = n;
-    c.out = d_rays;
-    hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c);
-    HIPCHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int rt2_camera_rays_host(rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, rt2_ray* rays) {
-    long long n = 0;
-    if (camera_rays_args("rt2_camera_rays_host", s, u, sh, rays, false, &n) != 0) return -1;
-    if (n == 0) return 0;
-    HIPCHECK(hipSetDevice(s->device));
-    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
-    hipStream_t st = s->host_stream;
-    if (surface_staging(s, s->d_surface_rays, s->surface_rays_cap, (size_t)n) != 0) return -1;
-    if (rt2_camera_rays(s, u, sh, s->d_surface_rays, st) != 0) return -1;
-    HIPCHECK(hipMemcpyAsync(rays, s->d_surface_rays, (size_t)n * sizeof(rt2_ray), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    return 0;
-}
-
-/* -------------------------------------------------------------------------
- * Preview shading queries (rt2_shade.h)
- * ----------------------------------------------------------------------- */
-namespace {
-// after the surface queries' codes: what rt2_scene_diag reports as the variant last launched
-enum : int { H_RES = -14, H_RES_L2 = -15, H_SCALAR = -16, H_BVH = -17 };
-
-// The argument checks of both shading entry points (`device`: the pointers' alignment too).
-int shade_rays_args(const char* who, const rt2_scene* s, const void* rays, int64_t n, const rt2_shade_opts* o,
-                    const void* out, int flags, bool device) {
-    const bool bad_ptr = n > 0 && (!rays || !out);
-    const bool misaligned = device && ((reinterpret_cast<uintptr_t>(rays) & 15) || (reinterpret_cast<uintptr_t>(out) & 15));
-    if (!s || !o || n < 0 || bad_ptr || misaligned || (flags & ~RT2_TRACE_SCALAR) || o->pad[0] || o->pad[1] ||
-        o->pad[2] || o->max_bounce < 1 || o->max_bounce > 256) {
-        rt2h::set_error(std::string(who) + ": bad argument (a scene and options, n >= 0, " +
-                        (device ? "rays and records aligned to 16 B, " : "rays and records, ") +
-                        "pad 0, max_bounce in 1 .. 256, flags 0 or RT2_TRACE_SCALAR)");
-        return -1;
-    }
-    if (n > 0 && s->traversal == RT2_TRAVERSAL_BVH && s->n_nodes == 0) {
-        rt2h::set_error(std::string(who) + ": bad argument (BVH traversal needs the node array)");
-        return -1;
-    }
-    return 0;
-}
-}  // namespace
-
-extern "C" int rt2_shade_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, const rt2_shade_opts* opts,
-                              rt2_shaded* d_out, int flags, void* stream) {
-    if (shade_rays_args("rt2_shade_rays", s, d_rays, n, opts, d_out, flags, true) != 0) return -1;
-    if (n == 0) return 0;
-    const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
-    HIPCHECK(hipSetDevice(s->device));
-    hipStream_t st = (hipStream_t)stream;
-    RenderParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.tri = s->d_tri;
-    p.n_tris = s->n_tris;
-    p.mfma_A = s->mfma_A;
-    p.mfma_kt_frag = s->d_mfma_kt;
-    p.nodes = s->d_nodes;
-    p.stack_slots = s->bvh_depth + 2;
-    p.item_counter = s->d_counters;
-    p.seg_counter = s->d_counters + 1;
-    // what trace_basic and shade_step read
-    p.unit_n = s->d_unit_n;
-    p.tri_mtl = s->d_mtl;
-    p.mats = s->d_mats;
-    p.n_mats = s->n_mats;
-    p.raw = s->d_raw;
-    p.texels = s->d_texels;
-    p.tex_desc = s->d_tex_desc;
-    p.n_tex = s->n_tex;
-    p.num_textures = std::min(s->n_tex, 5);  // the rule of rt2_surface_rays: the images bound, at most the five units
-    p.maxBounce = opts->max_bounce;
-    p.basicShadow = opts->shadow;
-    p.light[0] = opts->light[0];
-    p.light[1] = opts->light[1];
-    p.light[2] = opts->light[2];
-    ShadeParams q{d_rays, d_out, (long long)n};
-    // RT2_TRACE_AUTO: the matrix kernel at every ray count, the choice of rt2_trace_rays.  On config B it beat the
-    // scalar kernel in every round from 2^22 rays (0.83 against 4.99 ms with the shadow ray) down to one 64-ray chunk
-    // (52 against 289 us; profiles/shade_ab.json).
-    const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
-    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
-    if (matrix) {
-        const unsigned blocks = (unsigned)std::min<long long>(s->num_cus, (n + 1023) / 1024);
-        const bool resident = (s->n_tris + 31) / 32 <= kResGroups;
-        if (resident)
-            hipLaunchKernelGGL(shade_rays_k5r<kOccRes>, dim3(blocks), dim3(kOccRes.m.block), 0, st, p, q);
-        else
-            hipLaunchKernelGGL(shade_rays_k5r<kOccResL2>, dim3(blocks), dim3(kOccResL2.m.block), 0, st, p, q);
-        HIPCHECK(hipGetLastError());
-        s->last_kind = K_MFMA;
-        s->last_variant = resident ? H_RES : H_RES_L2;
-    } else {
-        for (long long i0 = 0; i0 < (long long)n; i0 += kQuerySlice) {
-            q.rays = d_rays + i0;
-            q.out = d_out + i0;
-            q.n = std::min<long long>(kQuerySlice, (long long)n - i0);
-            const unsigned blocks = (unsigned)((q.n + kQueryBlock - 1) / kQueryBlock);
-            if (bvh)
-                hipLaunchKernelGGL((shade_rays_scalar<kQueryBlock, true>), dim3(blocks), dim3(kQueryBlock),
-                                   (size_t)p.stack_slots * kQueryBlock * sizeof(int), st, p, q);
-            else
-                hipLaunchKernelGGL((shade_rays_scalar<kQueryBlock, false>), dim3(blocks), dim3(kQueryBlock), 0, st, p,
-                                   q);
-            HIPCHECK(hipGetLastError());
-        }
-        s->last_kind = bvh ? K_BVH : K_SMEM;
-        s->last_variant = bvh ? H_BVH : H_SCALAR;
-    }
-    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(s->last_launch, st));
-    s->last_launch_valid = true;
-    s->tests_per_seg = (unsigned long long)s->n_tris;
-    return 0;
-}
-
-extern "C" int rt2_shade_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n, const rt2_shade_opts* opts,
-                                   rt2_shaded* out, int flags) {
-    if (shade_rays_args("rt2_shade_rays_host", s, rays, n, opts, out, flags, false) != 0) return -1;
-    if (n == 0) return 0;
-    HIPCHECK(hipSetDevice(s->device));
-    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
-    hipStream_t st = s->host_stream;
-    if (surface_staging(s, s->d_shade_rays, s->shade_rays_cap, (size_t)n) != 0) return -1;
-    if (surface_staging(s, s->d_shade_out, s->shade_out_cap, (size_t)n) != 0) return -1;
-    HIPCHECK(hipMemcpyAsync(s->d_shade_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
-    if (rt2_shade_rays(s, s->d_shade_rays, n, opts, s->d_shade_out, flags, st) != 0) return -1;
-    HIPCHECK(hipMemcpyAsync(out, s->d_shade_out, (size_t)n * sizeof(rt2_shaded), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    return 0;
-}
-
-/* -------------------------------------------------------------------------
- * Radiance queries (rt2_radiance.h)
- * ----------------------------------------------------------------------- */
-namespace {
-// after the shading queries' codes: what rt2_scene_diag reports as the variant last launched
-enum : int { R_RES = -18, R_RES_L2 = -19, R_SCALAR = -20, R_BVH = -21 };
-
-// The argument checks of both radiance entry points (`device`: the pointers' alignment too).
-int radiance_rays_args(const char* who, const rt2_scene* s, const void* rays, int64_t n, const rt2_path_opts* o,
-                       const void* rng, const void* out, int flags, bool device) {
-    const bool bad_ptr = n > 0 && (!rays || !rng || !out);
-    const bool misaligned = device && n > 0 &&
-                            ((reinterpret_cast<uintptr_t>(rays) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) ||
-                             (reinterpret_cast<uintptr_t>(rng) & 3));
-    if (!s || !o || n < 0 || bad_ptr || misaligned || (flags & ~RT2_TRACE_SCALAR) || o->pad[0] || o->pad[1] ||
-        o->max_bounce < 1 || o->max_bounce > 256) {
-        rt2h::set_error(std::string(who) + ": bad argument (a scene and options, n >= 0, " +
-                        (device ? "rays and records aligned to 16 B and rng to 4 B, " : "rays, rng and records, ") +
-                        "pad 0, max_bounce in 1 .. 256, flags 0 or RT2_TRACE_SCALAR)");
-        return -1;
-    }
-    if (n > 0 && s->traversal == RT2_TRAVERSAL_BVH && s->n_nodes == 0) {
-        rt2h::set_error(std::string(who) + ": bad argument (BVH traversal needs the node array)");
-        return -1;
-    }
-    return 0;
-}
-
 // The argument checks of both path-camera entry points: camera_rays_args and the stream array.
 int path_rays_args(const char* who, const rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, const void* rng,
                    const void* rays, bool device, long long* n) {
@@ -2156,92 +1950,52 @@ int path_rays_args(const char* who, const rt2_scene* s, const rt2_uniforms* u, r
     }
     return 0;
 }
+
+void copy3(float* d, const rt2_vec4& v) {
+    d[0] = v.x;
+    d[1] = v.y;
+    d[2] = v.z;
+}
+
+// What CameraParams and PathRaysParams share: the view, the image and shard, the slab.
+template <class P>
+void camera_params(P& c, const rt2_uniforms* u, rt2_shard sh, long long n, rt2_ray* d_rays) {
+    std::memset(&c, 0, sizeof(c));
+    copy3(c.cam, u->cameraPos);
+    copy3(c.vpRight, u->viewportRight);
+    copy3(c.vpUp, u->viewportUp);
+    copy3(c.vpFront, u->viewportFront);
+    c.W = (int)u->width;
+    c.H = (int)u->height;
+    c.tile_rows = sh.tile_rows;
+    c.rank = sh.rank;
+    c.nranks = sh.nranks;
+    c.n = n;
+    c.out = d_rays;
+}
 }  // namespace
 
-extern "C" int rt2_radiance_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, const rt2_path_opts* opts,
-                                 uint32_t* d_rng, rt2_radiance* d_out, int flags, void* stream) {
-    if (radiance_rays_args("rt2_radiance_rays", s, d_rays, n, opts, d_rng, d_out, flags, true) != 0) return -1;
+extern "C" int rt2_camera_rays(rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, rt2_ray* d_rays, void* stream) {
+    long long n = 0;
+    if (camera_rays_args("rt2_camera_rays", s, u, sh, d_rays, true, &n) != 0) return -1;
     if (n == 0) return 0;
-    const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
     HIPCHECK(hipSetDevice(s->device));
-    hipStream_t st = (hipStream_t)stream;
-    RenderParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.tri = s->d_tri;
-    p.n_tris = s->n_tris;
-    p.mfma_A = s->mfma_A;
-    p.mfma_kt_frag = s->d_mfma_kt;
-    p.nodes = s->d_nodes;
-    p.stack_slots = s->bvh_depth + 2;
-    p.item_counter = s->d_counters;
-    p.seg_counter = s->d_counters + 1;
-    // what radiance_step reads
-    p.unit_n = s->d_unit_n;
-    p.tri_mtl = s->d_mtl;
-    p.mats = s->d_mats;
-    p.n_mats = s->n_mats;
-    p.raw = s->d_raw;
-    p.texels = s->d_texels;
-    p.tex_desc = s->d_tex_desc;
-    p.n_tex = s->n_tex;
-    p.num_textures = std::min(s->n_tex, 5);  // the rule of rt2_surface_rays: the images bound, at most the five units
-    p.maxBounce = opts->max_bounce;
-    p.envLight = opts->environmental_light;
-    RadianceParams q{d_rays, d_rng, d_out, (long long)n};
-    // RT2_TRACE_AUTO: the matrix kernel at every ray count, the choice of rt2_shade_rays.
-    const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
-    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
-    if (matrix) {
-        const unsigned blocks = (unsigned)std::min<long long>(s->num_cus, (n + 1023) / 1024);
-        const bool resident = (s->n_tris + 31) / 32 <= kResGroups;
-        if (resident)
-            hipLaunchKernelGGL(radiance_rays_k5r<kOccRes>, dim3(blocks), dim3(kOccRes.m.block), 0, st, p, q);
-        else
-            hipLaunchKernelGGL(radiance_rays_k5r<kOccResL2>, dim3(blocks), dim3(kOccResL2.m.block), 0, st, p, q);
-        HIPCHECK(hipGetLastError());
-        s->last_kind = K_MFMA;
-        s->last_variant = resident ? R_RES : R_RES_L2;
-    } else {
-        for (long long i0 = 0; i0 < (long long)n; i0 += kQuerySlice) {
-            q.rays = d_rays + i0;
-            q.rng = d_rng + i0;
-            q.out = d_out + i0;
-            q.n = std::min<long long>(kQuerySlice, (long long)n - i0);
-            const unsigned blocks = (unsigned)((q.n + kQueryBlock - 1) / kQueryBlock);
-            if (bvh)
-                hipLaunchKernelGGL((radiance_rays_scalar<kQueryBlock, true>), dim3(blocks), dim3(kQueryBlock),
-                                   (size_t)p.stack_slots * kQueryBlock * sizeof(int), st, p, q);
-            else
-                hipLaunchKernelGGL((radiance_rays_scalar<kQueryBlock, false>), dim3(blocks), dim3(kQueryBlock), 0, st,
-                                   p, q);
-            HIPCHECK(hipGetLastError());
-        }
-        s->last_kind = bvh ? K_BVH : K_SMEM;
-        s->last_variant = bvh ? R_BVH : R_SCALAR;
-    }
-    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(s->last_launch, st));
-    s->last_launch_valid = true;
-    s->tests_per_seg = (unsigned long long)s->n_tris;
+    CameraParams c;
+    camera_params(c, u, sh, n, d_rays);
+    hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c);
+    HIPCHECK(hipGetLastError());
     return 0;
 }
 
-extern "C" int rt2_radiance_rays_host(rt2_scene* s, const rt2_ray* rays, int64_t n, const rt2_path_opts* opts,
-                                      uint32_t* rng, rt2_radiance* out, int flags) {
-    if (radiance_rays_args("rt2_radiance_rays_host", s, rays, n, opts, rng, out, flags, false) != 0) return -1;
+extern "C" int rt2_camera_rays_host(rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, rt2_ray* rays) {
+    long long n = 0;
+    if (camera_rays_args("rt2_camera_rays_host", s, u, sh, rays, false, &n) != 0) return -1;
     if (n == 0) return 0;
-    HIPCHECK(hipSetDevice(s->device));
-    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    if (staging_begin(s, (size_t)n, false, 0) != 0) return -1;
     hipStream_t st = s->host_stream;
-    if (surface_staging(s, s->d_radiance_rays, s->radiance_rays_cap, (size_t)n) != 0) return -1;
-    if (surface_staging(s, s->d_radiance_rng, s->radiance_rng_cap, (size_t)n) != 0) return -1;
-    if (surface_staging(s, s->d_radiance_out, s->radiance_out_cap, (size_t)n) != 0) return -1;
-    HIPCHECK(hipMemcpyAsync(s->d_radiance_rays, rays, (size_t)n * sizeof(rt2_ray), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(s->d_radiance_rng, rng, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (rt2_radiance_rays(s, s->d_radiance_rays, n, opts, s->d_radiance_rng, s->d_radiance_out, flags, st) != 0)
-        return -1;
-    HIPCHECK(hipMemcpyAsync(out, s->d_radiance_out, (size_t)n * sizeof(rt2_radiance), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipMemcpyAsync(rng, s->d_radiance_rng, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    rt2_ray* d_rays = static_cast<rt2_ray*>(s->stage_rays.ptr);
+    if (rt2_camera_rays(s, u, sh, d_rays, st) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(rays, d_rays, (size_t)n * sizeof(rt2_ray), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     return 0;
 }
@@ -2253,30 +2007,14 @@ extern "C" int rt2_path_rays(rt2_scene* s, const rt2_uniforms* u, rt2_shard sh, 
     if (n == 0) return 0;
     HIPCHECK(hipSetDevice(s->device));
     PathRaysParams c;
-    std::memset(&c, 0, sizeof(c));
-    auto cp = [](float* d, const rt2_vec4& v) {
-        d[0] = v.x;
-        d[1] = v.y;
-        d[2] = v.z;
-    };
-    cp(c.cam, u->cameraPos);
-    cp(c.vpRight, u->viewportRight);
-    cp(c.vpUp, u->viewportUp);
-    cp(c.vpFront, u->viewportFront);
-    cp(c.pixR, u->pixelRight);
-    cp(c.pixU, u->pixelUp);
-    cp(c.defR, u->defocusDiskRight);
-    cp(c.defU, u->defocusDiskUp);
-    c.W = (int)u->width;
-    c.H = (int)u->height;
-    c.tile_rows = sh.tile_rows;
-    c.rank = sh.rank;
-    c.nranks = sh.nranks;
+    camera_params(c, u, sh, n, d_rays);
+    copy3(c.pixR, u->pixelRight);
+    copy3(c.pixU, u->pixelUp);
+    copy3(c.defR, u->defocusDiskRight);
+    copy3(c.defU, u->defocusDiskUp);
     c.frame = frame_index;
     c.reseed = reseed;
-    c.n = n;
     c.rng = d_rng;
-    c.out = d_rays;
     hipLaunchKernelGGL(path_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c);
     HIPCHECK(hipGetLastError());
     return 0;
@@ -2287,16 +2025,14 @@ extern "C" int rt2_path_rays_host(rt2_scene* s, const rt2_uniforms* u, rt2_shard
     long long n = 0;
     if (path_rays_args("rt2_path_rays_host", s, u, sh, rng, rays, false, &n) != 0) return -1;
     if (n == 0) return 0;
-    HIPCHECK(hipSetDevice(s->device));
-    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
+    if (staging_begin(s, (size_t)n, true, 0) != 0) return -1;
     hipStream_t st = s->host_stream;
-    if (surface_staging(s, s->d_radiance_rays, s->radiance_rays_cap, (size_t)n) != 0) return -1;
-    if (surface_staging(s, s->d_radiance_rng, s->radiance_rng_cap, (size_t)n) != 0) return -1;
-    if (!reseed)
-        HIPCHECK(hipMemcpyAsync(s->d_radiance_rng, rng, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (rt2_path_rays(s, u, sh, frame_index, reseed, s->d_radiance_rng, s->d_radiance_rays, st) != 0) return -1;
-    HIPCHECK(hipMemcpyAsync(rays, s->d_radiance_rays, (size_t)n * sizeof(rt2_ray), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipMemcpyAsync(rng, s->d_radiance_rng, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    rt2_ray* d_rays = static_cast<rt2_ray*>(s->stage_rays.ptr);
+    uint32_t* d_rng = static_cast<uint32_t*>(s->stage_rng.ptr);
+    if (!reseed) HIPCHECK(hipMemcpyAsync(d_rng, rng, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (rt2_path_rays(s, u, sh, frame_index, reseed, d_rng, d_rays, st) != 0) return -1;
+    HIPCHECK(hipMemcpyAsync(rays, d_rays, (size_t)n * sizeof(rt2_ray), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(rng, d_rng, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     return 0;
 }

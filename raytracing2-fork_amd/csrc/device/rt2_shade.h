@@ -140,18 +140,9 @@ template <OccSpec O>
 __global__ __launch_bounds__(O.m.block) __attribute__((amdgpu_waves_per_eu(O.m.waves))) void shade_rays_k5r(RenderParams p_arg,
                                                                                                            ShadeParams q) {
     constexpr MfmaSpec S = O.m;  // the closest-hit sweeps and the any-hit sweep share the frame and its records
-    __shared__ K5Resident rs;
-    res_load_records<S>(rs);
-    MfmaDiag dg;
-    const int lane = (int)lane_id();
-    const unsigned long long n_chunks = ((unsigned long long)q.n + 63) >> 6;
-    unsigned long long segs_w = 0;
-    const unsigned long long n_waves = (unsigned long long)gridDim.x * (S.block / 64);
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform to the compiler
-    for (unsigned long long c = (unsigned long long)blockIdx.x * (S.block / 64) + wave; c < n_chunks; c += n_waves) {
-        const RenderParams& p = kargs<RenderParams>();
-        const long long base = (long long)(c << 6);
-        const int live = (int)min(64ll, q.n - base);
+    query_chunks<S>(q.n, [&](const RenderParams& p, const h8* rec, long long base, int live, MfmaDiag& dg,
+                             unsigned long long& segs_w) {
+        const int lane = (int)lane_id();
         ShadeLane L;
         {
             // lanes of a ragged last chunk hold the chunk's first ray and never trace it; tmax is not used
@@ -190,7 +181,7 @@ __global__ __launch_bounds__(O.m.block) __attribute__((amdgpu_waves_per_eu(O.m.w
             float best = 1e38f, bestK = 1e38f * 1.0009765625f;
             int bi = -1;
             bool swept = false;
-            if (!__ballot(!query_finite(ro, rd))) swept = sweep_kt_res<S>(p, rs.rec, ro, rd, best, bi, bestK, dg, upper);
+            if (!__ballot(!query_finite(ro, rd))) swept = sweep_kt_res<S>(p, rec, ro, rd, best, bi, bestK, dg, upper);
             // a ray outside the filter's range or not finite (wave-uniform): the drain's exact code
             if (!swept) coop_each(act, ro, rd, p, best, bi);
             if (mine) shade_step(p, L, best, bi);
@@ -209,7 +200,7 @@ __global__ __launch_bounds__(O.m.block) __attribute__((amdgpu_waves_per_eu(O.m.w
             }
             bool occ = false, swept = false;
             if (!__ballot(!query_finite(so, sd)))
-                swept = sweep_kt_occ<O>(p, rs.rec, so, sd, 1e38f, 1e38f * 1.0009765625f, (pend >> 32) != 0, mine, occ);
+                swept = sweep_kt_occ<O>(p, rec, so, sd, 1e38f, 1e38f * 1.0009765625f, (pend >> 32) != 0, mine, occ);
             if (!swept) {
                 float best = 1e38f;
                 int bi = -1;
@@ -224,9 +215,7 @@ __global__ __launch_bounds__(O.m.block) __attribute__((amdgpu_waves_per_eu(O.m.w
         if (L.slot >= 0)  // one 16-byte store per ray, at the ray's own index
             *reinterpret_cast<float4*>(q.out + base + L.slot) =
                 make_float4(L.cum.x, L.cum.y, L.cum.z, __int_as_float(L.bc));
-    }
-    const RenderParams& p = kargs<RenderParams>();
-    if (lane == 0) atomicAdd(p.seg_counter, segs_w);
+    });
 }
 
 // One thread per ray: trace_basic as render_basic calls it, then the record.

@@ -105,18 +105,9 @@ __device__ __forceinline__ void surface_store(rt2_surface* out, long long i, con
 template <MfmaSpec S>
 __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves))) void surface_k5r(RenderParams p_arg,
                                                                                                       SurfaceParams q) {
-    __shared__ K5Resident rs;
-    res_load_records<S>(rs);
-    MfmaDiag dg;
-    const int lane = (int)lane_id();
-    const unsigned long long n_chunks = ((unsigned long long)q.n + 63) >> 6;
-    unsigned long long rays_w = 0;
-    const unsigned long long n_waves = (unsigned long long)gridDim.x * (S.block / 64);
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform to the compiler
-    for (unsigned long long c = (unsigned long long)blockIdx.x * (S.block / 64) + wave; c < n_chunks; c += n_waves) {
-        const RenderParams& p = kargs<RenderParams>();
-        const long long base = (long long)(c << 6);
-        const int live = (int)min(64ll, q.n - base);
+    query_chunks<S>(q.n, [&](const RenderParams& p, const h8* rec, long long base, int live, MfmaDiag& dg,
+                             unsigned long long& segs_w) {
+        const int lane = (int)lane_id();
         const bool mine = lane < live;
         const unsigned long long act = live == 64 ? ~0ull : (1ull << live) - 1ull;
         // lanes of a ragged last chunk carry the chunk's first ray (and its bound) and store nothing
@@ -126,14 +117,12 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
         float best = bound, bestK = bound * 1.0009765625f;
         int bi = -1;
         bool swept = false;
-        if (!__ballot(!query_finite(o, d))) swept = sweep_kt_res<S>(p, rs.rec, o, d, best, bi, bestK, dg, live > 32);
+        if (!__ballot(!query_finite(o, d))) swept = sweep_kt_res<S>(p, rec, o, d, best, bi, bestK, dg, live > 32);
         // a ray outside the filter's range or not finite (wave-uniform): the drain's exact code
         if (!swept) coop_each(act, o, d, p, best, bi, &bound);
         if (mine) surface_store(q.out, base + lane, surface_record(p, o, d, best, bi));
-        rays_w += (unsigned long long)live;
-    }
-    const RenderParams& p = kargs<RenderParams>();
-    if (lane == 0) atomicAdd(p.seg_counter, rays_w);
+        segs_w += (unsigned long long)live;
+    });
 }
 
 // One thread per ray: trace_rays_scalar's search, then the record.

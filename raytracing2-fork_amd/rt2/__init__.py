@@ -353,6 +353,25 @@ def _f3(v) -> C.Array:
     return (C.c_float * 3)(*map(float, v))
 
 
+def _ptr(x: int):
+    """A nullable address (a device array, a stream) as a ctypes argument."""
+    return C.c_void_p(x) if x else None
+
+
+def _pack_rays(who: str, origins, directions, tmax=None) -> np.ndarray:
+    """The RAY_DTYPE array of a blocking ray query: origins and directions
+    (n, 3), tmax None (0: unbounded), a scalar or (n,)."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise RT2Error(f"{who}: {len(o)} origins for {len(d)} directions")
+    rays = np.zeros(len(o), dtype=RAY_DTYPE)
+    rays["o"], rays["d"] = o, d
+    if tmax is not None:
+        rays["tmax"] = np.asarray(tmax, dtype=np.float32)
+    return rays
+
+
 class SceneData:
     """The reference's host scene arrays (rayTracing.cpp:1256-1293)."""
 
@@ -558,19 +577,18 @@ class Comm:
     def gather_slabs(self, slab_ptr: int, width: int, height: int, sh: Shard, root: int, image_ptr: int,
                      stream: int = 0) -> None:
         _check(lib().rt2_gather_slabs(self._p, C.c_void_p(slab_ptr), width, height, sh, root,
-                                      C.c_void_p(image_ptr) if image_ptr else None,
-                                      C.c_void_p(stream) if stream else None), "rt2_gather_slabs")
+                                      _ptr(image_ptr), _ptr(stream)), "rt2_gather_slabs")
 
     def wait(self, stream: int = 0) -> None:
         """rt2_comm_wait: the stream drained under the RT2_COMM_TIMEOUT_S deadline."""
-        _check(lib().rt2_comm_wait(self._p, C.c_void_p(stream) if stream else None), "rt2_comm_wait")
+        _check(lib().rt2_comm_wait(self._p, _ptr(stream)), "rt2_comm_wait")
 
 
 def unshard_slabs(gathered_ptr: int, max_rows: int, width: int, height: int, layout: Shard, image_ptr: int,
                   stream: int = 0) -> None:
     """Root-side un-interleave of [nranks][max_rows][width] 16-byte pixels (rt2_unshard_slabs)."""
     _check(lib().rt2_unshard_slabs(C.c_void_p(gathered_ptr), max_rows, width, height, layout, C.c_void_p(image_ptr),
-                                   C.c_void_p(stream) if stream else None), "rt2_unshard_slabs")
+                                   _ptr(stream)), "rt2_unshard_slabs")
 
 
 class Scene:
@@ -636,8 +654,7 @@ class Scene:
                accum8_ptr: int = 0, stream: int = 0) -> None:
         """Asynchronous device render into caller-owned device accumulators (rt2_render)."""
         _check(lib().rt2_render(self._p, C.byref(u), frame_begin, frame_count, sh, C.c_void_p(accum_ptr),
-                                C.c_void_p(accum8_ptr) if accum8_ptr else None,
-                                C.c_void_p(stream) if stream else None), "rt2_render")
+                                _ptr(accum8_ptr), _ptr(stream)), "rt2_render")
 
     def render_host(self, u: Uniforms, frame_begin: int, frame_count: int, sh: Optional[Shard] = None,
                     rgb8: bool = False):
@@ -657,8 +674,7 @@ class Scene:
         sum_ptr and, with sumsq_ptr, the means of the samples' squares to that one ((rows, W, 4) float32 each,
         aligned to 16 bytes, .w written 0)."""
         _check(lib().rt2_render_linear(self._p, C.byref(u), frame_begin, frame_count, sh, C.c_void_p(sum_ptr),
-                                       C.c_void_p(sumsq_ptr) if sumsq_ptr else None,
-                                       C.c_void_p(stream) if stream else None), "rt2_render_linear")
+                                       _ptr(sumsq_ptr), _ptr(stream)), "rt2_render_linear")
 
     def render_linear_host(self, u: Uniforms, frame_begin: int, frame_count: int, sh: Optional[Shard] = None,
                            moments: bool = False):
@@ -693,39 +709,24 @@ class Scene:
         directions (n, 3), tmax None (unbounded), a scalar or (n,).  Returns
         (dst float32[n], tri int32[n]); a miss has tri = -1 and dst = the ray's
         bound.  Indices are those of the triangle array the scene was made of."""
-        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
-        if len(o) != len(d):
-            raise RT2Error(f"trace_rays: {len(o)} origins for {len(d)} directions")
-        rays = np.zeros(len(o), dtype=RAY_DTYPE)
-        rays["o"], rays["d"] = o, d
-        if tmax is not None:
-            rays["tmax"] = np.asarray(tmax, dtype=np.float32)
-        hits = np.zeros(len(o), dtype=HIT_DTYPE)
+        rays = _pack_rays("trace_rays", origins, directions, tmax)
+        hits = np.zeros(len(rays), dtype=HIT_DTYPE)
         _check(lib().rt2_trace_rays_host(self._p, rays.ctypes.data, len(rays), hits.ctypes.data, int(flags)),
                "rt2_trace_rays_host")
         return hits["dst"].copy(), hits["tri"].copy()
 
     def trace_rays_device(self, rays_ptr: int, n: int, hits_ptr: int, flags: int = 0, stream: int = 0) -> None:
         """Asynchronous query over device arrays of n rt2_ray / rt2_hit records (rt2_trace_rays)."""
-        _check(lib().rt2_trace_rays(self._p, C.c_void_p(rays_ptr) if rays_ptr else None, int(n),
-                                    C.c_void_p(hits_ptr) if hits_ptr else None, int(flags),
-                                    C.c_void_p(stream) if stream else None), "rt2_trace_rays")
+        _check(lib().rt2_trace_rays(self._p, _ptr(rays_ptr), int(n), _ptr(hits_ptr), int(flags), _ptr(stream)),
+               "rt2_trace_rays")
 
     def occluded(self, origins, directions, tmax=None, flags: int = 0) -> np.ndarray:
         """Whether anything lies in front of each of n rays before its bound
         (rt2_occluded_host, blocking): the arguments of trace_rays; returns
         bool[n], equal to trace_rays(...)[1] >= 0 without the closest hit being
         found (a ray stops at its first accepted hit)."""
-        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
-        if len(o) != len(d):
-            raise RT2Error(f"occluded: {len(o)} origins for {len(d)} directions")
-        rays = np.zeros(len(o), dtype=RAY_DTYPE)
-        rays["o"], rays["d"] = o, d
-        if tmax is not None:
-            rays["tmax"] = np.asarray(tmax, dtype=np.float32)
-        out = np.full(len(o), 0xAA, dtype=np.uint8)
+        rays = _pack_rays("occluded", origins, directions, tmax)
+        out = np.full(len(rays), 0xAA, dtype=np.uint8)
         _check(lib().rt2_occluded_host(self._p, rays.ctypes.data, len(rays), out.ctypes.data, int(flags)),
                "rt2_occluded_host")
         if (out > 1).any():
@@ -734,9 +735,8 @@ class Scene:
 
     def occluded_device(self, rays_ptr: int, n: int, out_ptr: int, flags: int = 0, stream: int = 0) -> None:
         """Asynchronous occlusion query over a device array of n rt2_ray records into n bytes (rt2_occluded)."""
-        _check(lib().rt2_occluded(self._p, C.c_void_p(rays_ptr) if rays_ptr else None, int(n),
-                                  C.c_void_p(out_ptr) if out_ptr else None, int(flags),
-                                  C.c_void_p(stream) if stream else None), "rt2_occluded")
+        _check(lib().rt2_occluded(self._p, _ptr(rays_ptr), int(n), _ptr(out_ptr), int(flags), _ptr(stream)),
+               "rt2_occluded")
 
     def surface(self, origins, directions, tmax=None, flags: int = 0) -> np.ndarray:
         """What is at the closest hit of n rays (rt2_surface_rays_host, blocking):
@@ -746,24 +746,16 @@ class Scene:
         (it faces the ray), u and v the barycentric weights of b and c, albedo
         the surface's base colour (traceBasic with one bounce and no shadow).
         A miss has tri = mtl = mtl_type = -1, dst = the ray's bound and zeros."""
-        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
-        if len(o) != len(d):
-            raise RT2Error(f"surface: {len(o)} origins for {len(d)} directions")
-        rays = np.zeros(len(o), dtype=RAY_DTYPE)
-        rays["o"], rays["d"] = o, d
-        if tmax is not None:
-            rays["tmax"] = np.asarray(tmax, dtype=np.float32)
-        out = np.zeros(len(o), dtype=SURFACE_DTYPE)
+        rays = _pack_rays("surface", origins, directions, tmax)
+        out = np.zeros(len(rays), dtype=SURFACE_DTYPE)
         _check(lib().rt2_surface_rays_host(self._p, rays.ctypes.data, len(rays), out.ctypes.data, int(flags)),
                "rt2_surface_rays_host")
         return out
 
     def surface_device(self, rays_ptr: int, n: int, out_ptr: int, flags: int = 0, stream: int = 0) -> None:
         """Asynchronous surface query over device arrays of n rt2_ray / rt2_surface records (rt2_surface_rays)."""
-        _check(lib().rt2_surface_rays(self._p, C.c_void_p(rays_ptr) if rays_ptr else None, int(n),
-                                      C.c_void_p(out_ptr) if out_ptr else None, int(flags),
-                                      C.c_void_p(stream) if stream else None), "rt2_surface_rays")
+        _check(lib().rt2_surface_rays(self._p, _ptr(rays_ptr), int(n), _ptr(out_ptr), int(flags), _ptr(stream)),
+               "rt2_surface_rays")
 
     def camera_rays(self, u: Uniforms, sh: Optional[Shard] = None) -> np.ndarray:
         """The deterministic primary ray of every pixel of the shard's slab
@@ -777,8 +769,7 @@ class Scene:
 
     def camera_rays_device(self, u: Uniforms, sh: Shard, rays_ptr: int, stream: int = 0) -> None:
         """Asynchronous: the slab's primary rays into a device array of rt2_ray records (rt2_camera_rays)."""
-        _check(lib().rt2_camera_rays(self._p, C.byref(u), sh, C.c_void_p(rays_ptr) if rays_ptr else None,
-                                     C.c_void_p(stream) if stream else None), "rt2_camera_rays")
+        _check(lib().rt2_camera_rays(self._p, C.byref(u), sh, _ptr(rays_ptr), _ptr(stream)), "rt2_camera_rays")
 
     def feature_buffers(self, u: Uniforms, sh: Optional[Shard] = None, flags: int = 0) -> dict:
         """First-hit feature buffers of a view, for a denoiser, picking or
@@ -822,13 +813,8 @@ class Scene:
         rgb is what traceBasic returns for the ray, segments the closest-hit
         searches it cost (bounces plus the shadow ray).  Every segment is
         unbounded: there is no tmax."""
-        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
-        if len(o) != len(d):
-            raise RT2Error(f"shade_rays: {len(o)} origins for {len(d)} directions")
-        rays = np.zeros(len(o), dtype=RAY_DTYPE)
-        rays["o"], rays["d"] = o, d
-        out = np.zeros(len(o), dtype=SHADED_DTYPE)
+        rays = _pack_rays("shade_rays", origins, directions)
+        out = np.zeros(len(rays), dtype=SHADED_DTYPE)
         opts = shade_opts(light, shadow, max_bounce)
         _check(lib().rt2_shade_rays_host(self._p, rays.ctypes.data, len(rays), C.byref(opts), out.ctypes.data,
                                          int(flags)), "rt2_shade_rays_host")
@@ -838,9 +824,8 @@ class Scene:
                           max_bounce: int = 1, flags: int = 0, stream: int = 0) -> None:
         """Asynchronous shading query over device arrays of n rt2_ray / rt2_shaded records (rt2_shade_rays)."""
         opts = shade_opts(light, shadow, max_bounce)
-        _check(lib().rt2_shade_rays(self._p, C.c_void_p(rays_ptr) if rays_ptr else None, int(n), C.byref(opts),
-                                    C.c_void_p(out_ptr) if out_ptr else None, int(flags),
-                                    C.c_void_p(stream) if stream else None), "rt2_shade_rays")
+        _check(lib().rt2_shade_rays(self._p, _ptr(rays_ptr), int(n), C.byref(opts), _ptr(out_ptr), int(flags),
+                                    _ptr(stream)), "rt2_shade_rays")
 
     def preview(self, u: Uniforms, sh: Optional[Shard] = None, flags: int = 0) -> np.ndarray:
         """The preview image of a view through the shading query: the slab's
@@ -882,14 +867,11 @@ class Scene:
         segments the closest-hit searches the path cost) and the streams'
         states after the paths' last draws.  The caller's rng array is not
         modified.  Every segment is unbounded: there is no tmax."""
-        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        rays = _pack_rays("radiance", origins, directions)
         state = np.array(rng, dtype=np.uint32).reshape(-1)  # a copy
-        if len(o) != len(d) or len(o) != len(state):
-            raise RT2Error(f"radiance: {len(o)} origins, {len(d)} directions, {len(state)} rng states")
-        rays = np.zeros(len(o), dtype=RAY_DTYPE)
-        rays["o"], rays["d"] = o, d
-        out = np.zeros(len(o), dtype=RADIANCE_DTYPE)
+        if len(rays) != len(state):
+            raise RT2Error(f"radiance: {len(rays)} rays for {len(state)} rng states")
+        out = np.zeros(len(rays), dtype=RADIANCE_DTYPE)
         opts = path_opts(max_bounce, environmental_light)
         _check(lib().rt2_radiance_rays_host(self._p, rays.ctypes.data, len(rays), C.byref(opts), state.ctypes.data,
                                             out.ctypes.data, int(flags)), "rt2_radiance_rays_host")
@@ -900,10 +882,8 @@ class Scene:
         """Asynchronous radiance query over device arrays of n rt2_ray records, uint32 stream states (read and
         written) and rt2_radiance records (rt2_radiance_rays)."""
         opts = path_opts(max_bounce, environmental_light)
-        _check(lib().rt2_radiance_rays(self._p, C.c_void_p(rays_ptr) if rays_ptr else None, int(n), C.byref(opts),
-                                       C.c_void_p(rng_ptr) if rng_ptr else None,
-                                       C.c_void_p(out_ptr) if out_ptr else None, int(flags),
-                                       C.c_void_p(stream) if stream else None), "rt2_radiance_rays")
+        _check(lib().rt2_radiance_rays(self._p, _ptr(rays_ptr), int(n), C.byref(opts), _ptr(rng_ptr), _ptr(out_ptr),
+                                       int(flags), _ptr(stream)), "rt2_radiance_rays")
 
     def path_rays(self, u: Uniforms, frame_index: int, sh: Optional[Shard] = None, rng=None):
         """The path tracer's jittered camera rays of the slab's pixels
@@ -934,9 +914,7 @@ class Scene:
         """Asynchronous: the slab's path-tracer camera rays into a device array of rt2_ray records, the streams'
         states in a device array of uint32 (rt2_path_rays)."""
         _check(lib().rt2_path_rays(self._p, C.byref(u), sh, int(frame_index) & 0xFFFFFFFF, int(bool(reseed)),
-                                   C.c_void_p(rng_ptr) if rng_ptr else None,
-                                   C.c_void_p(rays_ptr) if rays_ptr else None,
-                                   C.c_void_p(stream) if stream else None), "rt2_path_rays")
+                                   _ptr(rng_ptr), _ptr(rays_ptr), _ptr(stream)), "rt2_path_rays")
 
     def radiance_image(self, u: Uniforms, frame_index: int, sh: Optional[Shard] = None, flags: int = 0):
         """The linear (HDR) image of one frame of a view: the mean over
@@ -1124,15 +1102,14 @@ def has_variant(v: int) -> bool:
 
 def resolve_rgba32f(accum_ptr: int, n_pixels: int, frames: int, out_ptr: int, stream: int = 0) -> None:
     _check(lib().rt2_resolve_rgba32f(C.c_void_p(accum_ptr), n_pixels, frames, C.c_void_p(out_ptr),
-                                     C.c_void_p(stream) if stream else None), "resolve")
+                                     _ptr(stream)), "resolve")
 
 
 def resolve_tonemap(sum_ptr: int, n_pixels: int, frames: int, out_ptr: int, stream: int = 0) -> None:
     """Device resolve of a linear sum (Scene.render_linear) to the render's display value: srgb1(aces1(sum /
     frames)) per channel, alpha = 1 (rt2_resolve_tonemap); asynchronous."""
-    _check(lib().rt2_resolve_tonemap(C.c_void_p(sum_ptr) if sum_ptr else None, n_pixels, frames,
-                                     C.c_void_p(out_ptr) if out_ptr else None,
-                                     C.c_void_p(stream) if stream else None), "rt2_resolve_tonemap")
+    _check(lib().rt2_resolve_tonemap(_ptr(sum_ptr), n_pixels, frames, _ptr(out_ptr), _ptr(stream)),
+           "rt2_resolve_tonemap")
 
 
 def resolve_rgb8_reference(acc8: np.ndarray, frames: int) -> np.ndarray:
