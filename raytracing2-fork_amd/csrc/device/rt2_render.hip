@@ -68,9 +68,13 @@ void set_error(const std::string& msg);
     } while (0)
 
 constexpr int kCounters = 32;  // [0] items, [1..7] stats + wave-end, [8..] kernel diagnostics
-struct Staging {  // a device buffer grown on demand (staging_grow)
+struct Staging {  // a device buffer grown on demand (staging_grow), freed with the scene
     void* ptr = nullptr;
     size_t cap = 0;  // bytes
+    template <class T>
+    T* as() const {
+        return static_cast<T*>(ptr);
+    }
 };
 struct rt2_scene {
     int device = 0;
@@ -99,21 +103,15 @@ struct rt2_scene {
     rt2_cluster_table slot_table = {};          // ... its table over the slot groups
     std::vector<int32_t> slot_tri;              // ... slot s holds triangle slot_tri[s]
     float mfma_A = 0.0f;                        // max |a_i| over the in-range triangles
-    float4* d_fb = nullptr;                     // frame_split scratch (per-frame colours; linear renders: moment slots)
     uchar4* d_texels = nullptr;                 // textures, RGBA8
     int4* d_tex_desc = nullptr;
     int n_tex = 0;
-    size_t fb_bytes = 0;
     int bvh_root = 0;                           // BVH v2 stack entry of node 0
     int recs_ok = 0;                            // BVH v3 fast-path precondition on the boxes
     int split_frames = 1;                       // frame-major (frame, pixel) items when F > 1
     unsigned long long frame_scratch_cap = 2ull << 30;  // bytes of per-frame planes per launch
     int cost_order = 0;                         // order items by the previous launch's per-pixel cost (opt-in)
-    uint32_t* d_cost = nullptr;                 // per-pixel cost map of the last launch
-    uint32_t* d_order = nullptr;                // pixel order for the next launch
-    uint32_t* d_hist = nullptr;                 // 32 counters
     unsigned long long cost_npix = 0;           // pixels the cost map describes (0 = none)
-    unsigned long long cost_cap = 0;
     int cost_key[4] = {0, 0, 0, 0};             // W, tile_rows, rank, nranks the map belongs to
     hipEvent_t last_launch = nullptr;           // renders of one scene are ordered (shared scratch)
     bool last_launch_valid = false;
@@ -127,24 +125,20 @@ struct rt2_scene {
     unsigned long long diag[kCounters] = {};
     int num_cus = 256;
     size_t max_lds = 65536;
-    // rt2_render_host: device buffers reused across calls (grown on demand,
-    // freed with the scene) and the stream the blocking wrapper runs on
+    // Scratch of the launches, grown inside a launch on the caller's stream (DESIGN.md "The render launcher"):
+    Staging fb;                     // frame_split scratch (per-frame colours; linear renders: moment slots)
+    Staging cost, order, hist;      // cost order: per-pixel cost map of the last launch, pixel order for the next
+                                    // launch, 32 counters
+    Staging region_ctr;             // 8 item-region counters, 128 B apart
+    // The stream the blocking wrappers run on, and their device buffers, reused across calls.  One set of images
+    // serves rt2_render_host and rt2_render_linear_host, and one set of staging the ray queries' and ray generators'
+    // seven *_host entry points, because every one of those calls runs on host_stream and ends in
+    // hipStreamSynchronize: no buffer is in use when the next call starts.
     hipStream_t host_stream = nullptr;
-    float4* d_host_acc = nullptr;   // float accumulator
-    float4* d_host_res = nullptr;   // resolved mean
-    uint4* d_host_acc8 = nullptr;   // 8-bit path sums
-    uint8_t* d_host_rgb8 = nullptr; // 8-bit path result (3 B per pixel)
-    size_t host_cap = 0;            // pixels the four buffers hold
-    // rt2_render_linear_host: sums, second moments and their two resolved means, kept like the above
-    float4* d_lin[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t lin_cap = 0;             // pixels each of the four holds
-    // The ray queries' and ray generators' seven *_host entry points: staging for the rays, the RNG words and the
-    // output bytes, kept like the above.  One set serves them all, because every one of those calls runs on
-    // host_stream and ends in hipStreamSynchronize: no buffer is in use when the next call starts.
-    Staging stage_rays, stage_rng, stage_out;
+    Staging host_img[4];            // float sums; 8-bit sums or second moments; the two resolved outputs
+    Staging stage_rays, stage_rng, stage_out;  // the rays, the RNG words and the output bytes
     int query_arm = 0;                // experiment build: A/B arm of the resident query kernel
     int occluded_arm = 0;             // experiment build: A/B arm of occluded_k5r
-    unsigned long long* d_region_ctr = nullptr;  // 8 item-region counters, 128 B apart
     unsigned long long* wave_log = nullptr;  // diagnostic wave timeline (rt2_scene_set_wave_log)
     uint32_t wave_log_n = 0;
 };
@@ -566,21 +560,13 @@ extern "C" void rt2_scene_destroy(rt2_scene* s) {
     (void)hipFree(s->d_mfma_k16_bnd);
     (void)hipFree(s->d_mfma_kt);
     (void)hipFree(s->d_slot);
-    (void)hipFree(s->d_fb);
-    for (float4* b : s->d_lin) (void)hipFree(b);
-    (void)hipFree(s->d_cost);
-    (void)hipFree(s->d_order);
-    (void)hipFree(s->d_hist);
     if (s->last_launch) (void)hipEventDestroy(s->last_launch);
     (void)hipFree(s->d_texels);
     (void)hipFree(s->d_tex_desc);
     (void)hipFree(s->d_counters);
-    (void)hipFree(s->d_host_acc);
-    (void)hipFree(s->d_host_res);
-    (void)hipFree(s->d_host_acc8);
-    (void)hipFree(s->d_host_rgb8);
-    for (const Staging* b : {&s->stage_rays, &s->stage_rng, &s->stage_out}) (void)hipFree(b->ptr);
-    (void)hipFree(s->d_region_ctr);
+    for (const Staging* b : {&s->fb, &s->cost, &s->order, &s->hist, &s->region_ctr, &s->host_img[0], &s->host_img[1],
+                             &s->host_img[2], &s->host_img[3], &s->stage_rays, &s->stage_rng, &s->stage_out})
+        (void)hipFree(b->ptr);
     if (s->host_stream) (void)hipStreamDestroy(s->host_stream);
     delete s;
 }
@@ -637,6 +623,11 @@ hipError_t launch_k(const RenderParams& p, int blocks, size_t lds, hipStream_t s
 }
 #define RT2_VARIANT(ID, KIND, KERNEL, BLOCK, NAME, ...) \
     Variant { ID, KIND, BLOCK, launch_k<KERNEL, BLOCK>, KERNEL, NAME __VA_OPT__(, ) __VA_ARGS__ }
+// A product kernel and its linear twin, written once: TEMPLATE<SPEC> as ID and TEMPLATE<lin(SPEC)> as
+// ID + kLinearTwin, with the parent's block, max_groups and slot flag and its name plus "/lin".
+#define RT2_PRODUCT(ID, KIND, TEMPLATE, SPEC, BLOCK, NAME, ...)                  \
+    RT2_VARIANT(ID, KIND, TEMPLATE<SPEC>, BLOCK, NAME __VA_OPT__(, ) __VA_ARGS__), \
+        RT2_VARIANT(ID + kLinearTwin, KIND, TEMPLATE<lin(SPEC)>, BLOCK, NAME "/lin" __VA_OPT__(, ) __VA_ARGS__)
 
 // product kernels
 constexpr SmemSpec kSmemDefault{.block = 256, .group = 8, .filter = Filter::Max3, .tail = Tail::Coop,
@@ -730,6 +721,16 @@ constexpr MfmaSpec kt_tiles_flow4() {
     x.lean = true;
     return x;
 }
+// The shipped matrix-filter specs (353 .. 356, 380; the comments in kVariants).  The ray queries take the resident
+// frame of 353 before its per-ray, pair-loop, cluster and slot pieces, and 355's as it is (kQueryRes, kQueryResL2).
+constexpr MfmaSpec kResFrame = kt_win(kt_res(false, false, true, 4), kResWin);
+constexpr MfmaSpec kResSlabFrame = kt_win(kt_res(false, true, true), kResWin);
+constexpr MfmaSpec kt_product(MfmaSpec frame) { return kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(frame)))))); }
+constexpr MfmaSpec kRes = kt_product(kResFrame);
+constexpr MfmaSpec kResSlab = kt_product(kResSlabFrame);
+constexpr MfmaSpec kResL2 = kt_win(kt_res(true, false, true, 4), kResWin);
+constexpr MfmaSpec kResL2Slab = kt_win(kt_res(true, true, true), kResWin);
+constexpr MfmaSpec kTiles = kt_tiles_flow4();
 constexpr Bvh3Spec kBvhDefault{.block = 256, .thresh = 16, .slab = Slab::Markstein, .waves = 5, .diag = false};
 
 #ifdef RT2_EXPERIMENTS
@@ -746,13 +747,14 @@ constexpr Bvh3Spec bvh3_x(int t, Slab sl, int w, bool diag = false) {
 
 constexpr Variant kVariants[] = {
     RT2_VARIANT(0, K_SMEM, render_smem<kSmemDefault>, 256, "smem/256/max3f8/coop32/w6/lockstep"),  // default (<= kSmemMaxTris)
-    RT2_VARIANT(109, K_BVH4, render_bvh4<kBvhDefault>, 256, "bvh4/256/t16/w5"),           // default (BVH traversal)
-    RT2_VARIANT(86, K_TILED, render_tiled<kTiledLarge>, 512, "tiled/512/max3f4"),          // > kSmemMaxTris
-    RT2_VARIANT(92, K_ASSIST, render_assist<kAssist12>, 768, "assist12/max3f8/w6"),        // < 4 items per lane
-    RT2_VARIANT(136, K_SMEM, render_smem<kSmemDefault>, 256, "smem/256/max3f8/coop32/w6/lockstep"),  // variant 0 forced (id 0 = automatic)
+    // every product kernel with its linear twin (kLinearTwin; 0's is 136's)
+    RT2_PRODUCT(109, K_BVH4, render_bvh4, kBvhDefault, 256, "bvh4/256/t16/w5"),           // default (BVH traversal)
+    RT2_PRODUCT(86, K_TILED, render_tiled, kTiledLarge, 512, "tiled/512/max3f4"),          // > kSmemMaxTris
+    RT2_PRODUCT(92, K_ASSIST, render_assist, kAssist12, 768, "assist12/max3f8/w6"),        // < 4 items per lane
+    RT2_PRODUCT(136, K_SMEM, render_smem, kSmemDefault, 256, "smem/256/max3f8/coop32/w6/lockstep"),  // variant 0 forced (id 0 = automatic)
     // the matrix filter with every wave reading the records from L2 (DESIGN.md "The 5-product form"): U, -V, X from
     // the first K-half, the left-out m.z slots bounded in the threshold; 3 waves per SIMD
-    RT2_VARIANT(227, K_MFMA, render_mfma<kMfmaK5>, 256, "mfma/256/k5/coop8/w3/imax/minred/ymma/t12/llds/ser4/cmp"),
+    RT2_PRODUCT(227, K_MFMA, render_mfma, kMfmaK5, 256, "mfma/256/k5/coop8/w3/imax/minred/ymma/t12/llds/ser4/cmp"),
     // scenes of <= 256 groups (8,192 triangles; config B: 38, W: 57, K: 89): the resident kernel (rt2_k5_resident.h:
     // records in LDS for the whole launch, 38 groups, the rest read from L2) with the threshold in the K-slots
     // (DESIGN.md "The threshold in the K-slots"), each ray's own W, issue priority by phase; fair-share issue
@@ -763,24 +765,13 @@ constexpr Variant kVariants[] = {
     // per ray (DESIGN.md "The camera end point once per pixel")
     // and sweep the scene's slot image (DESIGN.md "Slot order"), a compact cluster that at most 8 rays need with 8-row
     // products (DESIGN.md "8-row products")
-    RT2_VARIANT(353, K_MFMA, render_mfma_k5r<kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin)))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups, true),
-    RT2_VARIANT(354, K_MFMA, render_mfma_k5r<kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin)))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups, true),
-    RT2_VARIANT(355, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, false, true, 4), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
-    RT2_VARIANT(356, K_MFMA, render_mfma_k5r<kt_win(kt_res(true, true, true), kResWin)>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw", kResL2Groups),
+    RT2_PRODUCT(353, K_MFMA, render_mfma_k5r, kRes, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups, true),
+    RT2_PRODUCT(354, K_MFMA, render_mfma_k5r, kResSlab, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups, true),
+    RT2_PRODUCT(355, K_MFMA, render_mfma_k5r, kResL2, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
+    RT2_PRODUCT(356, K_MFMA, render_mfma_k5r, kResL2Slab, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw", kResL2Groups),
     // the default above 8,192 triangles: the LDS-tiled kernel (rt2_k5_tiles.h; 19-group tiles, fragments in
     // registers) with the threshold in the K-slots, each ray's own W in the bound
-    RT2_VARIANT(380, K_MFMA, render_mfma_k5t<kt_tiles_flow4()>, 1024, "mfmat5/1024/kt4/tile19/coop0/w4/cmp/regs/perm/lw/flowp/lean"),
-    // the linear twins of every variant above (kLinearTwin; 0's is 136's)
-    RT2_VARIANT(1109, K_BVH4, render_bvh4<lin(kBvhDefault)>, 256, "bvh4/256/t16/w5/lin"),
-    RT2_VARIANT(1086, K_TILED, render_tiled<lin(kTiledLarge)>, 512, "tiled/512/max3f4/lin"),
-    RT2_VARIANT(1092, K_ASSIST, render_assist<lin(kAssist12)>, 768, "assist12/max3f8/w6/lin"),
-    RT2_VARIANT(1136, K_SMEM, render_smem<lin(kSmemDefault)>, 256, "smem/256/max3f8/coop32/w6/lockstep/lin"),
-    RT2_VARIANT(1227, K_MFMA, render_mfma<lin(kMfmaK5)>, 256, "mfma/256/k5/coop8/w3/imax/minred/ymma/t12/llds/ser4/cmp/lin"),
-    RT2_VARIANT(1353, K_MFMA, render_mfma_k5r<lin(kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/lin", kResGroups, true),
-    RT2_VARIANT(1354, K_MFMA, render_mfma_k5r<lin(kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin))))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/lin", kResGroups, true),
-    RT2_VARIANT(1355, K_MFMA, render_mfma_k5r<lin(kt_win(kt_res(true, false, true, 4), kResWin))>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4/lin", kResL2Groups),
-    RT2_VARIANT(1356, K_MFMA, render_mfma_k5r<lin(kt_win(kt_res(true, true, true), kResWin))>, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/fair/dpp/lean/lw/lin", kResL2Groups),
-    RT2_VARIANT(1380, K_MFMA, render_mfma_k5t<lin(kt_tiles_flow4())>, 1024, "mfmat5/1024/kt4/tile19/coop0/w4/cmp/regs/perm/lw/flowp/lean/lin"),
+    RT2_PRODUCT(380, K_MFMA, render_mfma_k5t, kTiles, 1024, "mfmat5/1024/kt4/tile19/coop0/w4/cmp/regs/perm/lw/flowp/lean"),
 #ifdef RT2_EXPERIMENTS
     // One knob away from a shipping matrix-filter kernel, plus one diagnostic build per template (DESIGN.md "Tried
     // and measured"; earlier generations are in git history).
@@ -959,73 +950,106 @@ extern "C" int rt2_variant_occupancy(int v, int* api_blocks, int* num_regs, int*
     return 0;
 }
 
-// rt2_render (linear = false: d_sumsq is null) and rt2_render_linear (linear =
-// true: d_accum is d_sum, d_accum8 null) after their argument checks: one
-// selection logic, one schedule; the linear render launches the chosen
-// variant's twin (id + kLinearTwin) and folds a second set of frame planes.
-static int render_launch(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count, rt2_shard sh,
-                         float* d_accum, uint32_t* d_accum8, float* d_sumsq, bool linear, void* stream) {
-    const int rows = rt2_shard_rows((int)u->height, sh);
-    // frame-major items keep one colour plane per frame: beyond frame_scratch_cap
-    // of planes (or 2^32 items), render consecutive frame chunks — the
-    // accumulation stays in frame order, so the sums are unchanged
-    if (!u->basicShading && s->split_frames && frame_count > 1) {
-        const unsigned long long npix = (unsigned long long)rows * u->width;
-        // (a linear render with moments keeps two planes per frame)
-        const unsigned long long per_frame = npix * sizeof(float4) * (d_sumsq ? 2u : 1u);
-        unsigned long long chunk = std::max<unsigned long long>(1, s->frame_scratch_cap / per_frame);
-        chunk = std::min<unsigned long long>(chunk, 0xfffffffeull / std::max<unsigned long long>(npix, 1));
-        if (chunk < frame_count) {
-            for (unsigned long long f0 = 0; f0 < frame_count; f0 += chunk) {
-                const uint32_t fc = (uint32_t)std::min<unsigned long long>(chunk, frame_count - f0);
-                const int rc = render_launch(s, u, frame_begin + (uint32_t)f0, fc, sh, d_accum, d_accum8, d_sumsq,
-                                             linear, stream);
-                if (rc != 0) return rc;
-            }
-            return 0;
-        }
-    }
-    HIPCHECK(hipSetDevice(s->device));
-    hipStream_t st = (hipStream_t)stream;
+/* -------------------------------------------------------------------------
+ * What every launch shares (renders and ray queries): the scene's RenderParams, the scratch, the launch order
+ * ----------------------------------------------------------------------- */
+namespace {
+// Grows one of the scene's buffers to `bytes`.  `drain`: the stream whose work may still use the old buffer, drained
+// before it is freed (the blocking wrappers' host_stream).  Null for the scratch a launch grows on its caller's
+// stream: there hipFree's own device synchronisation is the wait.
+int staging_grow(Staging& b, size_t bytes, const hipStream_t* drain = nullptr) {
+    if (bytes <= b.cap) return 0;
+    if (drain) HIPCHECK(hipStreamSynchronize(*drain));
+    (void)hipFree(b.ptr);
+    b.ptr = nullptr;
+    b.cap = 0;
+    HIPCHECK(hipMalloc(&b.ptr, bytes));
+    b.cap = bytes;
+    return 0;
+}
 
+// What every launch's search reads.
+RenderParams scene_params(const rt2_scene* s) {
     RenderParams p;
     std::memset(&p, 0, sizeof(p));
     p.tri = s->d_tri;
-    p.unit_n = s->d_unit_n;
-    p.plk = s->plk_ok ? s->d_plk : nullptr;
-    p.plk_A = s->plk_A;
+    p.n_tris = s->n_tris;
     p.mfma_A = s->mfma_A;
-    p.mfma_k16_frag = s->d_mfma_k16;
-    p.mfma_k16_tau = s->d_mfma_k16_tau;
-    p.mfma_k16_bnd = s->d_mfma_k16_bnd;
     p.mfma_kt_frag = s->d_mfma_kt;
+    p.nodes = s->d_nodes;
+    p.stack_slots = s->bvh_depth + 2;
+    p.item_counter = s->d_counters;
+    p.seg_counter = s->d_counters + 1;
+    return p;
+}
+
+// ... and what the shaders read of the materials and textures (the renders, surface_record, shade_step and
+// radiance_step).
+void scene_shading_params(const rt2_scene* s, RenderParams& p) {
+    p.unit_n = s->d_unit_n;
     p.tri_mtl = s->d_mtl;
+    p.mats = s->d_mats;
+    p.n_mats = s->n_mats;
     p.raw = s->d_raw;
     p.texels = s->d_texels;
     p.tex_desc = s->d_tex_desc;
     p.n_tex = s->n_tex;
+    p.num_textures = std::min(s->n_tex, 5);  // a ray query has no uniforms: the images bound, at most the five units
+}
+
+void copy3(float* d, const rt2_vec4& v) {
+    d[0] = v.x;
+    d[1] = v.y;
+    d[2] = v.z;
+}
+
+// Launches of one scene share its counters and scratch (frame planes, cost map, pixel order): a launch waits for
+// the scene's previous one, whatever stream that was issued on ...
+int launch_begin(rt2_scene* s, hipStream_t st) {
+    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
+    return 0;
+}
+// ... and leaves the event the next one waits on.
+int launch_end(rt2_scene* s, hipStream_t st) {
+    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(s->last_launch, st));
+    s->last_launch_valid = true;
+    s->tests_per_seg = (unsigned long long)s->n_tris;
+    return 0;
+}
+}  // namespace
+
+/* -------------------------------------------------------------------------
+ * The render launcher (DESIGN.md "The render launcher"): render_launch and its steps, in the order they run
+ * ----------------------------------------------------------------------- */
+namespace {
+// A render's RenderParams: the scene's, the uniforms' view and image, the shard's slab.
+RenderParams render_params(const rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count,
+                           rt2_shard sh, int rows) {
+    RenderParams p = scene_params(s);
+    scene_shading_params(s, p);
     p.num_textures = u->numTextures;
-    p.mats = s->d_mats;
-    p.n_tris = s->n_tris;
-    p.n_mats = s->n_mats;
+    p.plk = s->plk_ok ? s->d_plk : nullptr;
+    p.plk_A = s->plk_A;
+    p.mfma_k16_frag = s->d_mfma_k16;
+    p.mfma_k16_tau = s->d_mfma_k16_tau;
+    p.mfma_k16_bnd = s->d_mfma_k16_bnd;
+    p.wave_log = s->wave_log;
+    p.wave_log_n = s->wave_log_n;
+    p.tile_tris = kTileTris;
     p.W = (int)u->width;
     p.H = (int)u->height;
     p.maxBounce = u->maxBounceCount;
     p.R = u->numRaysPerPixel;
     p.envLight = u->environmentalLight;
-    auto cp = [](float* d, const rt2_vec4& v) {
-        d[0] = v.x;
-        d[1] = v.y;
-        d[2] = v.z;
-    };
-    cp(p.cam, u->cameraPos);
-    cp(p.vpRight, u->viewportRight);
-    cp(p.vpUp, u->viewportUp);
-    cp(p.vpFront, u->viewportFront);
-    cp(p.pixR, u->pixelRight);
-    cp(p.pixU, u->pixelUp);
-    cp(p.defR, u->defocusDiskRight);
-    cp(p.defU, u->defocusDiskUp);
+    copy3(p.cam, u->cameraPos);
+    copy3(p.vpRight, u->viewportRight);
+    copy3(p.vpUp, u->viewportUp);
+    copy3(p.vpFront, u->viewportFront);
+    copy3(p.pixR, u->pixelRight);
+    copy3(p.pixU, u->pixelUp);
+    copy3(p.defR, u->defocusDiskRight);
+    copy3(p.defU, u->defocusDiskUp);
     p.frame_begin = frame_begin;
     p.frame_count = frame_count;
     p.tile_rows = sh.tile_rows;
@@ -1033,132 +1057,111 @@ static int render_launch(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_beg
     p.nranks = sh.nranks;
     p.n_pix = (unsigned long long)rows * (unsigned long long)p.W;
     p.n_items = p.n_pix;
-    if (p.n_pix >= 0xffffffffull) {
-        rt2h::set_error("rt2_render: more than 2^32-1 pixels in one shard");
-        return -1;
-    }
-    p.accum = reinterpret_cast<float4*>(d_accum);
-    // the linear sink never writes 8-bit sums: its kernels read d_sumsq from this field (lin_accum_sq)
-    p.accum8 = linear ? reinterpret_cast<uint4*>(d_sumsq) : reinterpret_cast<uint4*>(d_accum8);
-    p.item_counter = s->d_counters;
-    p.seg_counter = s->d_counters + 1;
-    p.tile_tris = kTileTris;
-    p.wave_log = s->wave_log;
-    p.wave_log_n = s->wave_log_n;
+    return p;
+}
 
-    // renders of one scene share its counters and scratch (frame planes, cost
-    // map, pixel order): a render waits for the scene's previous one, whatever
-    // stream that was issued on
-    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
+// The counters a render starts from: items, the 8 item regions, the diagnostic wave ends.
+int counters_reset(rt2_scene* s, RenderParams& p, hipStream_t st) {
     HIPCHECK(hipMemsetAsync(s->d_counters, 0, sizeof(unsigned long long), st));
     // items in 8 contiguous regions, one per group of workgroups sharing an
     // XCD's L2 (blockIdx % 8): neighbouring pixels' rays walk the same BVH
     // lines in one L2 (config C BVH: 2,701 vs 2,783 ms; brute force ±0)
-    if (!s->d_region_ctr) HIPCHECK(hipMalloc(&s->d_region_ctr, 8 * 128));
-    HIPCHECK(hipMemsetAsync(s->d_region_ctr, 0, 8 * 128, st));
-    p.region_ctr = s->d_region_ctr;
+    if (staging_grow(s->region_ctr, 8 * 128) != 0) return -1;
+    HIPCHECK(hipMemsetAsync(s->region_ctr.ptr, 0, 8 * 128, st));
+    p.region_ctr = s->region_ctr.as<unsigned long long>();
     HIPCHECK(hipMemsetAsync(s->d_counters + 6, 0xff, sizeof(unsigned long long), st));  // diag: min wave end
     HIPCHECK(hipMemsetAsync(s->d_counters + 7, 0, sizeof(unsigned long long), st));     // diag: max wave end
-    p.nodes = s->d_nodes;
-    p.stack_slots = s->bvh_depth + 2;
-    if (u->basicShading) {  // traceBasic preview: one thread per pixel
-        p.basicShadow = u->basicShadingShadow;
-        cp(p.light, u->basicShadingLightPosition);
-        constexpr int kBasicBlock = 256;
-        const unsigned long long blocks = (p.n_items + kBasicBlock - 1) / kBasicBlock;
-        if (s->traversal == RT2_TRAVERSAL_BVH) {
-            const size_t lds = (size_t)p.stack_slots * kBasicBlock * sizeof(int);
-            hipLaunchKernelGGL((render_basic<kBasicBlock, true>), dim3((unsigned)blocks), dim3(kBasicBlock), lds, st,
-                               p);
-            s->last_kind = K_BVH;
-        } else {
-            hipLaunchKernelGGL((render_basic<kBasicBlock, false>), dim3((unsigned)blocks), dim3(kBasicBlock), 0, st,
-                               p);
-            s->last_kind = K_SMEM;
-        }
+    return 0;
+}
+
+// The traceBasic preview: one thread per pixel, every frame the same image.
+int launch_basic(rt2_scene* s, const rt2_uniforms* u, RenderParams& p, uint32_t frame_count, hipStream_t st) {
+    p.basicShadow = u->basicShadingShadow;
+    copy3(p.light, u->basicShadingLightPosition);
+    constexpr int kBasicBlock = 256;
+    const unsigned long long blocks = (p.n_items + kBasicBlock - 1) / kBasicBlock;
+    if (s->traversal == RT2_TRAVERSAL_BVH) {
+        const size_t lds = (size_t)p.stack_slots * kBasicBlock * sizeof(int);
+        hipLaunchKernelGGL((render_basic<kBasicBlock, true>), dim3((unsigned)blocks), dim3(kBasicBlock), lds, st, p);
+        s->last_kind = K_BVH;
+    } else {
+        hipLaunchKernelGGL((render_basic<kBasicBlock, false>), dim3((unsigned)blocks), dim3(kBasicBlock), 0, st, p);
+        s->last_kind = K_SMEM;
+    }
+    HIPCHECK(hipGetLastError());
+    if (launch_end(s, st) != 0) return -1;
+    s->last_variant = -1;
+    s->samples += p.n_items * (unsigned long long)frame_count;
+    return 0;
+}
+
+// Several frames: frame-major (frame, pixel) items into a scratch buffer, then frame_accumulate (finer work items:
+// a shorter tail).  The scratch holds the frames' colour planes and, for a linear render with moments, their moment
+// planes behind them; without frame split such a render keeps the moment slots of its whole-pixel items in one plane.
+int frame_scratch(rt2_scene* s, RenderParams& p, uint32_t frame_count, bool moments) {
+    p.frame_split = frame_count > 1 && s->split_frames && p.n_pix * frame_count < 0xffffffffull;
+    if (!p.frame_split && !moments) return 0;
+    const size_t planes = p.frame_split ? (size_t)frame_count * (moments ? 2u : 1u) : 1u;
+    if (staging_grow(s->fb, (size_t)p.n_pix * planes * sizeof(float4)) != 0) return -1;
+    p.frame_buf = s->fb.as<float4>();
+    if (p.frame_split) p.n_items = p.n_pix * frame_count;
+    return 0;
+}
+
+// Cost-ordered items: the previous launch's per-pixel costs (same slab) give this launch's pixel order, most
+// expensive first (a shorter tail).
+int cost_order_prepare(rt2_scene* s, RenderParams& p, const rt2_uniforms* u, rt2_shard sh, hipStream_t st) {
+    if (!s->cost_order) return 0;
+    const size_t bytes = (size_t)p.n_pix * sizeof(uint32_t);
+    if (bytes > s->cost.cap) s->cost_npix = 0;  // a new map describes nothing yet
+    if (staging_grow(s->cost, bytes) != 0 || staging_grow(s->order, bytes) != 0 ||
+        staging_grow(s->hist, 32 * sizeof(uint32_t)) != 0)
+        return -1;
+    uint32_t *d_cost = s->cost.as<uint32_t>(), *d_order = s->order.as<uint32_t>(), *d_hist = s->hist.as<uint32_t>();
+    const int key[4] = {(int)u->width, sh.tile_rows, sh.rank, sh.nranks};
+    const bool valid = s->cost_npix == p.n_pix && std::memcmp(key, s->cost_key, sizeof(key)) == 0;
+    const unsigned long long runs = p.n_pix / 64;
+    if (valid && runs > 0) {
+        const unsigned blocks = (unsigned)std::min<unsigned long long>((runs + 255) / 256, 2048);
+        HIPCHECK(hipMemsetAsync(d_hist, 0, 32 * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(cost_histogram, dim3(blocks), dim3(256), 0, st, d_cost, runs, d_hist);
+        hipLaunchKernelGGL(cost_offsets, dim3(1), dim3(64), 0, st, d_hist);
+        hipLaunchKernelGGL(cost_scatter, dim3(blocks), dim3(256), 0, st, d_cost, runs, d_hist, d_order);
         HIPCHECK(hipGetLastError());
-        if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
-        HIPCHECK(hipEventRecord(s->last_launch, st));
-        s->last_launch_valid = true;
-        s->last_variant = -1;
-        s->samples += p.n_items * (unsigned long long)frame_count;
-        s->tests_per_seg = (unsigned long long)s->n_tris;
-        return 0;
+        p.order = d_order;
+        p.n_runs = (uint32_t)runs;
     }
-    // several frames: frame-major (frame, pixel) items into a scratch buffer,
-    // then frame_accumulate (finer work items: a shorter tail)
-    if (frame_count > 1 && s->split_frames && p.n_pix * frame_count < 0xffffffffull) {
-        // (a linear render with moments: the frames' moment planes behind the colour planes)
-        const size_t need = (size_t)p.n_pix * frame_count * sizeof(float4) * (d_sumsq ? 2u : 1u);
-        if (need > s->fb_bytes) {
-            if (s->d_fb) HIPCHECK(hipFree(s->d_fb));
-            s->d_fb = nullptr;
-            s->fb_bytes = 0;
-            HIPCHECK(hipMalloc(&s->d_fb, need));
-            s->fb_bytes = need;
-        }
-        p.frame_split = 1;
-        p.frame_buf = s->d_fb;
-        p.n_items = p.n_pix * frame_count;
-    }
-    if (d_sumsq && !p.frame_split) {  // the moment slots of whole-pixel items: one plane
-        const size_t need = (size_t)p.n_pix * sizeof(float4);
-        if (need > s->fb_bytes) {
-            if (s->d_fb) HIPCHECK(hipFree(s->d_fb));
-            s->d_fb = nullptr;
-            s->fb_bytes = 0;
-            HIPCHECK(hipMalloc(&s->d_fb, need));
-            s->fb_bytes = need;
-        }
-        p.frame_buf = s->d_fb;
-    }
-    // cost-ordered items: the previous launch's per-pixel costs (same slab)
-    // give this launch's pixel order, most expensive first (a shorter tail)
-    if (s->cost_order) {
-        if (s->cost_cap < p.n_pix) {
-            (void)hipFree(s->d_cost);
-            (void)hipFree(s->d_order);
-            s->d_cost = s->d_order = nullptr;
-            s->cost_cap = 0;
-            s->cost_npix = 0;
-            HIPCHECK(hipMalloc(&s->d_cost, p.n_pix * sizeof(uint32_t)));
-            HIPCHECK(hipMalloc(&s->d_order, p.n_pix * sizeof(uint32_t)));
-            if (!s->d_hist) HIPCHECK(hipMalloc(&s->d_hist, 32 * sizeof(uint32_t)));
-            s->cost_cap = p.n_pix;
-        }
-        const int key[4] = {(int)u->width, sh.tile_rows, sh.rank, sh.nranks};
-        const bool valid = s->cost_npix == p.n_pix && std::memcmp(key, s->cost_key, sizeof(key)) == 0;
-        const unsigned long long runs = p.n_pix / 64;
-        if (valid && runs > 0) {
-            const unsigned blocks = (unsigned)std::min<unsigned long long>((runs + 255) / 256, 2048);
-            HIPCHECK(hipMemsetAsync(s->d_hist, 0, 32 * sizeof(uint32_t), st));
-            hipLaunchKernelGGL(cost_histogram, dim3(blocks), dim3(256), 0, st, s->d_cost, runs, s->d_hist);
-            hipLaunchKernelGGL(cost_offsets, dim3(1), dim3(64), 0, st, s->d_hist);
-            hipLaunchKernelGGL(cost_scatter, dim3(blocks), dim3(256), 0, st, s->d_cost, runs, s->d_hist, s->d_order);
-            HIPCHECK(hipGetLastError());
-            p.order = s->d_order;
-            p.n_runs = (uint32_t)runs;
-        }
-        // the cost map keeps each item's start clock in the pixel's own slot:
-        // with frame-major items several frames of one pixel run at once, so
-        // only frame 0's item of each pixel measures (one
-        // writer per slot; a frame-split launch's map is its frame 0's cost)
-        p.cost_out = s->d_cost;
-        s->cost_npix = p.n_pix;
-        std::memcpy(s->cost_key, key, sizeof(key));
-    }
-    // explicit variant (rt2_scene_set_variant) when it exists in this build,
-    // matches the traversal and can hold the scene; otherwise the automatic
-    // choice: the matrix-core filter kernels (the scalar-path kernel when the
-    // scene is outside the filter's range)
+    // the cost map keeps each item's start clock in the pixel's own slot:
+    // with frame-major items several frames of one pixel run at once, so
+    // only frame 0's item of each pixel measures (one
+    // writer per slot; a frame-split launch's map is its frame 0's cost)
+    p.cost_out = d_cost;
+    s->cost_npix = p.n_pix;
+    std::memcpy(s->cost_key, key, sizeof(key));
+    return 0;
+}
+
+// The variant rt2_scene_set_variant asked for, or null: none set, or one this launch cannot take.
+const Variant* forced_variant(const rt2_scene* s, bool linear) {
+    const Variant* V = s->variant > 0 ? find_variant(s->variant) : nullptr;
+    if (!V) return nullptr;
     const int n_groups = (s->n_tris + 31) / 32;
-    const Variant* VP = s->variant > 0 ? find_variant(s->variant) : nullptr;
-    if (VP && ((s->traversal == RT2_TRAVERSAL_BVH) != is_bvh(VP->kind))) VP = nullptr;
-    if (VP && VP->max_groups > 0 && n_groups > VP->max_groups) VP = nullptr;  // cannot hold this scene
-    if (VP && VP->kind == K_MFMA && !s->mfma_ok) VP = nullptr;              // scene outside the filter's range
-    if (VP && linear && !linear_twin(*VP)) VP = nullptr;                    // an experiment variant without a twin
+    const bool refused = (s->traversal == RT2_TRAVERSAL_BVH) != is_bvh(V->kind)  // the other traversal's kernel
+                         || (V->max_groups > 0 && n_groups > V->max_groups)      // cannot hold this scene
+                         || (V->kind == K_MFMA && !s->mfma_ok)                   // scene outside the filter's range
+                         || (linear && !linear_twin(*V));                        // an experiment variant without a twin
+    return refused ? nullptr : V;
+}
+
+// The kernel of a launch of n_items items: the explicit variant (rt2_scene_set_variant) when it exists in this
+// build, matches the traversal and can hold the scene; otherwise the automatic choice: the matrix-core filter
+// kernels (the scalar-path kernel when the scene is outside the filter's range).  A linear render takes the
+// choice's twin.
+int choose_variant(const rt2_scene* s, unsigned long long n_items, bool linear, const Variant** out) {
+    const Variant* VP = forced_variant(s, linear);
     if (!VP && s->traversal == RT2_TRAVERSAL_BVH) VP = find_variant(kDefaultBvh);
     if (!VP) {
+        const int n_groups = (s->n_tris + 31) / 32;
         int vi = s->n_tris <= kSmemMaxTris ? kDefaultBrute : kLargeScene;
         if (s->mfma_ok && find_variant(kMfma)) {
             // the filter on the matrix cores (rt2_mfma.h) for whole images and
@@ -1179,7 +1182,7 @@ static int render_launch(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_beg
                 // fair share, so that they also end together (DESIGN.md
                 // "Fair-share issue priority")
                 const unsigned long long lanes = (unsigned long long)s->num_cus * (unsigned long long)find_variant(kMfmaRes)->block;
-                const bool slab = p.n_items < kResSlabItems * lanes;
+                const bool slab = n_items < kResSlabItems * lanes;
                 vi = n_groups <= kResGroups ? (slab ? kMfmaResSlab : kMfmaRes) : (slab ? kMfmaResL2Slab : kMfmaResL2);
             } else if (find_variant(kMfmaTiles)) {
                 vi = kMfmaTiles;
@@ -1197,12 +1200,17 @@ static int render_launch(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_beg
             int occ0 = 0;
             HIPCHECK(variant_occupancy(*W, &occ0, 0));
             const unsigned long long lanes = (unsigned long long)s->num_cus * (unsigned long long)std::max(occ0, 1) * W->block;
-            if (p.n_items < 4 * lanes) vi = kSlab;
+            if (n_items < 4 * lanes) vi = kSlab;
         }
         VP = find_variant(vi);
     }
-    if (linear) VP = linear_twin(*VP);  // every variant chosen above has one
-    const Variant& V = *VP;
+    *out = linear ? linear_twin(*VP) : VP;  // every variant chosen above has a twin
+    return 0;
+}
+
+// V's launch geometry for the items of p: the item regions, the LDS bytes and the BVH stack, the workgroups, the
+// assist kernel's shares and the slot image.
+int launch_geometry(rt2_scene* s, const Variant& V, RenderParams& p, size_t* lds_out, unsigned long long* blocks_out) {
     // XCD-group item regions serve the BVH walk's L2 locality; the brute-force
     // kernels read the same records for every ray, so they take items from one
     // counter in dispatch order, which spreads neighbouring 64-pixel runs over
@@ -1247,7 +1255,6 @@ static int render_launch(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_beg
         const int rays_per_block = V.kind == K_SPLIT ? 64 : V.block;  // split: S waves per 64 rays
         blocks = std::min(blocks, (p.n_items + rays_per_block - 1) / rays_per_block);
     }
-    blocks = std::max(blocks, 1ull);
     if (V.slot) {
         if (!s->d_slot) {
             rt2h::set_error("rt2_render: the scene has no slot image");
@@ -1255,43 +1262,112 @@ static int render_launch(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_beg
         }
         p.mfma_kt_frag = reinterpret_cast<const _Float16*>(s->d_slot);
     }
-    s->last_variant = V.id;
-    HIPCHECK(V.launch(p, (int)blocks, lds, st));
+    *lds_out = lds;
+    *blocks_out = std::max(blocks, 1ull);
+    return 0;
+}
+
+// frame_accumulate over `planes`: the frames' planes folded into `sum` in frame order.
+int frames_fold(const RenderParams& p, const float4* planes, float4* sum, uint4* sum8, hipStream_t st) {
+    hipLaunchKernelGGL(frame_accumulate, dim3((unsigned)((p.n_pix + 255) / 256)), dim3(256), 0, st, planes, p.n_pix,
+                       p.frame_count, sum, sum8);
     HIPCHECK(hipGetLastError());
-    if (p.frame_split) {
-        hipLaunchKernelGGL(frame_accumulate, dim3((unsigned)((p.n_pix + 255) / 256)), dim3(256), 0, st, p.frame_buf,
-                           p.n_pix, frame_count, p.accum, linear ? (uint4*)nullptr : p.accum8);
-        HIPCHECK(hipGetLastError());
-        if (d_sumsq) {  // the frames' second moments, in the same order
-            hipLaunchKernelGGL(frame_accumulate, dim3((unsigned)((p.n_pix + 255) / 256)), dim3(256), 0, st,
-                               p.frame_buf + (size_t)p.n_pix * frame_count, p.n_pix, frame_count,
-                               reinterpret_cast<float4*>(d_sumsq), (uint4*)nullptr);
-            HIPCHECK(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+// rt2_render (linear = false: d_sumsq is null) and rt2_render_linear (linear =
+// true: d_accum is d_sum, d_accum8 null) after their argument checks: one
+// selection logic, one schedule; the linear render launches the chosen
+// variant's twin (id + kLinearTwin) and folds a second set of frame planes.
+static int render_launch(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count, rt2_shard sh,
+                         float* d_accum, uint32_t* d_accum8, float* d_sumsq, bool linear, void* stream) {
+    const int rows = rt2_shard_rows((int)u->height, sh);
+    // frame-major items keep one colour plane per frame: beyond frame_scratch_cap
+    // of planes (or 2^32 items), render consecutive frame chunks — the
+    // accumulation stays in frame order, so the sums are unchanged
+    if (!u->basicShading && s->split_frames && frame_count > 1) {
+        const unsigned long long npix = (unsigned long long)rows * u->width;
+        // (a linear render with moments keeps two planes per frame)
+        const unsigned long long per_frame = npix * sizeof(float4) * (d_sumsq ? 2u : 1u);
+        unsigned long long chunk = std::max<unsigned long long>(1, s->frame_scratch_cap / per_frame);
+        chunk = std::min<unsigned long long>(chunk, 0xfffffffeull / std::max<unsigned long long>(npix, 1));
+        if (chunk < frame_count) {
+            for (unsigned long long f0 = 0; f0 < frame_count; f0 += chunk) {
+                const uint32_t fc = (uint32_t)std::min<unsigned long long>(chunk, frame_count - f0);
+                const int rc = render_launch(s, u, frame_begin + (uint32_t)f0, fc, sh, d_accum, d_accum8, d_sumsq,
+                                             linear, stream);
+                if (rc != 0) return rc;
+            }
+            return 0;
         }
     }
-    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(s->last_launch, st));
-    s->last_launch_valid = true;
+    HIPCHECK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+
+    RenderParams p = render_params(s, u, frame_begin, frame_count, sh, rows);
+    if (p.n_pix >= 0xffffffffull) {
+        rt2h::set_error("rt2_render: more than 2^32-1 pixels in one shard");
+        return -1;
+    }
+    p.accum = reinterpret_cast<float4*>(d_accum);
+    // the linear sink never writes 8-bit sums: its kernels read d_sumsq from this field (lin_accum_sq)
+    p.accum8 = linear ? reinterpret_cast<uint4*>(d_sumsq) : reinterpret_cast<uint4*>(d_accum8);
+    if (launch_begin(s, st) != 0 || counters_reset(s, p, st) != 0) return -1;
+    if (u->basicShading) return launch_basic(s, u, p, frame_count, st);
+    if (frame_scratch(s, p, frame_count, d_sumsq != nullptr) != 0) return -1;
+    if (cost_order_prepare(s, p, u, sh, st) != 0) return -1;
+    const Variant* V = nullptr;
+    size_t lds = 0;
+    unsigned long long blocks = 0;
+    if (choose_variant(s, p.n_items, linear, &V) != 0 || launch_geometry(s, *V, p, &lds, &blocks) != 0) return -1;
+    s->last_variant = V->id;
+    HIPCHECK(V->launch(p, (int)blocks, lds, st));
+    HIPCHECK(hipGetLastError());
+    if (p.frame_split) {
+        if (frames_fold(p, p.frame_buf, p.accum, linear ? nullptr : p.accum8, st) != 0) return -1;
+        // the frames' second moments, in the same order
+        if (d_sumsq && frames_fold(p, p.frame_buf + (size_t)p.n_pix * frame_count, reinterpret_cast<float4*>(d_sumsq),
+                                   nullptr, st) != 0)
+            return -1;
+    }
+    if (launch_end(s, st) != 0) return -1;
     s->samples += p.n_pix * (unsigned long long)p.R * (unsigned long long)frame_count;
-    s->tests_per_seg = (unsigned long long)s->n_tris;
+    return 0;
+}
+
+// How the argument checks of rt2_render, rt2_render_linear and their _host forms differ.
+struct RenderArgRules {
+    const char* fn;
+    const char* out;  // the first output's name; null: both outputs may be null (rt2_render_host)
+    bool aligned;     // the two outputs are device sums aligned to 16 bytes (rt2_render_linear)
+    bool preview;     // basicShading is a render: the preview, which ignores numRaysPerPixel (rt2_render)
+};
+// ... and the checks; *rows = the slab's rows.
+static int render_args(const RenderArgRules& a, const rt2_scene* s, const rt2_uniforms* u, rt2_shard sh,
+                       const void* out0, const void* out1, int* rows) {
+    const auto bad = [&](const std::string& what) {
+        rt2h::set_error(std::string(a.fn) + ": bad argument: " + what);
+        return -1;
+    };
+    if (!s) return bad("null scene");
+    if (!u) return bad("null uniforms");
+    if (a.out && !out0) return bad(std::string("null ") + a.out);
+    if (a.aligned && (reinterpret_cast<uintptr_t>(out0) % 16 != 0 || reinterpret_cast<uintptr_t>(out1) % 16 != 0))
+        return bad("d_sum and d_sumsq must be aligned to 16 bytes");
+    if (u->basicShading && !a.preview)
+        return bad("basicShading: the preview has no tonemap, rt2_render gives its linear value");
+    if (!u->basicShading && u->numRaysPerPixel < 1) return bad("numRaysPerPixel must be >= 1");
+    if (u->width < 1 || u->height < 1) return bad("width and height must be >= 1");
+    *rows = rt2_shard_rows((int)u->height, sh);
+    if (*rows < 0) return bad("bad shard");
     return 0;
 }
 
 extern "C" int rt2_render(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count,
                           rt2_shard sh, float* d_accum, uint32_t* d_accum8, void* stream) {
-    if (!s || !u || !d_accum) {
-        rt2h::set_error("rt2_render: null argument");
-        return -1;
-    }
-    if ((!u->basicShading && u->numRaysPerPixel < 1) || u->width < 1 || u->height < 1) {
-        rt2h::set_error("rt2_render: numRaysPerPixel, width and height must be >= 1");
-        return -1;
-    }
-    const int rows = rt2_shard_rows((int)u->height, sh);
-    if (rows < 0) {
-        rt2h::set_error("rt2_render: bad shard");
-        return -1;
-    }
+    int rows = 0;
+    if (render_args({"rt2_render", "d_accum", false, true}, s, u, sh, d_accum, d_accum8, &rows) != 0) return -1;
     if (frame_count == 0 || rows == 0) return 0;
     return render_launch(s, u, frame_begin, frame_count, sh, d_accum, d_accum8, nullptr, false, stream);
 }
@@ -1346,61 +1422,47 @@ extern "C" int rt2_resolve_rgb8_reference(const uint32_t* acc8, int64_t n, uint3
     return 0;
 }
 
-// Grows the scene's render_host buffers to `n` pixels.  On failure the
-// buffers stay owned by the scene (freed by rt2_scene_destroy): no leak on any
-// error path.
-static int host_buffers(rt2_scene* s, size_t n) {
+// The blocking renders' start: the scene's device, host_stream and its four host images for n pixels (16 bytes
+// each; out1_bytes for the second resolved output), the float sums zeroed and, with `second`, the second accumulator.
+// On failure the images stay owned by the scene (freed by rt2_scene_destroy): no leak on any error path.
+static int host_images(rt2_scene* s, size_t n, bool second, size_t out1_bytes) {
+    HIPCHECK(hipSetDevice(s->device));
     if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
-    if (n <= s->host_cap) return 0;
-    HIPCHECK(hipStreamSynchronize(s->host_stream));
-    (void)hipFree(s->d_host_acc);
-    (void)hipFree(s->d_host_res);
-    (void)hipFree(s->d_host_acc8);
-    (void)hipFree(s->d_host_rgb8);
-    s->d_host_acc = s->d_host_res = nullptr;
-    s->d_host_acc8 = nullptr;
-    s->d_host_rgb8 = nullptr;
-    s->host_cap = 0;
-    HIPCHECK(hipMalloc(&s->d_host_acc, n * sizeof(float4)));
-    HIPCHECK(hipMalloc(&s->d_host_res, n * sizeof(float4)));
-    HIPCHECK(hipMalloc(&s->d_host_acc8, n * sizeof(uint4)));
-    HIPCHECK(hipMalloc(&s->d_host_rgb8, n * 3));
-    s->host_cap = n;
+    const size_t bytes[4] = {n * sizeof(float4), n * sizeof(float4), n * sizeof(float4), out1_bytes};
+    for (int i = 0; i < 4; i++)
+        if (staging_grow(s->host_img[i], bytes[i], &s->host_stream) != 0) return -1;
+    HIPCHECK(hipMemsetAsync(s->host_img[0].ptr, 0, bytes[0], s->host_stream));
+    if (second) HIPCHECK(hipMemsetAsync(s->host_img[1].ptr, 0, bytes[1], s->host_stream));
+    return 0;
+}
+
+// The mean over `frames` of the float sums in host image `acc`, resolved into host image `res` and copied to `out`.
+static int host_mean(rt2_scene* s, int acc, int res, size_t n, uint32_t frames, float* out) {
+    if (rt2_resolve_rgba32f(s->host_img[acc].as<float>(), (int64_t)n, frames, s->host_img[res].as<float>(),
+                            s->host_stream) != 0)
+        return -1;
+    HIPCHECK(hipMemcpyAsync(out, s->host_img[res].ptr, n * sizeof(float4), hipMemcpyDeviceToHost, s->host_stream));
     return 0;
 }
 
 extern "C" int rt2_render_host(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count,
                                rt2_shard sh, float* out_rgba, uint8_t* out_rgb8) {
-    if (!s || !u) {
-        rt2h::set_error("rt2_render_host: null argument");
-        return -1;
-    }
-    const int rows = rt2_shard_rows((int)u->height, sh);
-    if (rows < 0) {
-        rt2h::set_error("rt2_render_host: bad shard");
-        return -1;
-    }
+    int rows = 0;
+    if (render_args({"rt2_render_host", nullptr, false, true}, s, u, sh, out_rgba, out_rgb8, &rows) != 0) return -1;
     const size_t n = (size_t)rows * u->width;
     if (n == 0 || frame_count == 0) return 0;
-    HIPCHECK(hipSetDevice(s->device));
-    if (host_buffers(s, n) != 0) return -1;
+    if (host_images(s, n, out_rgb8 != nullptr, n * 3) != 0) return -1;
     hipStream_t st = s->host_stream;
-    HIPCHECK(hipMemsetAsync(s->d_host_acc, 0, n * sizeof(float4), st));
-    if (out_rgb8) HIPCHECK(hipMemsetAsync(s->d_host_acc8, 0, n * sizeof(uint4), st));
-    if (rt2_render(s, u, frame_begin, frame_count, sh, reinterpret_cast<float*>(s->d_host_acc),
-                   out_rgb8 ? reinterpret_cast<uint32_t*>(s->d_host_acc8) : nullptr, st) != 0)
+    uint4* const d_acc8 = out_rgb8 ? s->host_img[1].as<uint4>() : nullptr;
+    if (rt2_render(s, u, frame_begin, frame_count, sh, s->host_img[0].as<float>(),
+                   reinterpret_cast<uint32_t*>(d_acc8), st) != 0)
         return -1;
-    if (out_rgba) {
-        if (rt2_resolve_rgba32f(reinterpret_cast<const float*>(s->d_host_acc), (int64_t)n, frame_count,
-                                reinterpret_cast<float*>(s->d_host_res), st) != 0)
-            return -1;
-        HIPCHECK(hipMemcpyAsync(out_rgba, s->d_host_res, n * sizeof(float4), hipMemcpyDeviceToHost, st));
-    }
+    if (out_rgba && host_mean(s, 0, 2, n, frame_count, out_rgba) != 0) return -1;
     if (out_rgb8) {
-        hipLaunchKernelGGL(resolve_rgb8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                           s->d_host_acc8, (long long)n, (float)frame_count, s->d_host_rgb8);
+        hipLaunchKernelGGL(resolve_rgb8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_acc8,
+                           (long long)n, (float)frame_count, s->host_img[3].as<uint8_t>());
         HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpyAsync(out_rgb8, s->d_host_rgb8, n * 3, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(out_rgb8, s->host_img[3].ptr, n * 3, hipMemcpyDeviceToHost, st));
     }
     HIPCHECK(hipStreamSynchronize(st));  // only this render's stream, not the device
     return 0;
@@ -1409,31 +1471,10 @@ extern "C" int rt2_render_host(rt2_scene* s, const rt2_uniforms* u, uint32_t fra
 /* -------------------------------------------------------------------------
  * Linear renders (rt2_path.h end_path_linear; the twins of kVariants)
  * ----------------------------------------------------------------------- */
-// The argument checks of rt2_render_linear (device = true: the pointers'
-// alignment too) and rt2_render_linear_host; *rows = the slab's rows.
-static int render_linear_args(const char* fn, const rt2_scene* s, const rt2_uniforms* u, rt2_shard sh,
-                              const float* sum, const float* sumsq, bool device, int* rows) {
-    const auto bad = [&](const char* what) {
-        rt2h::set_error(std::string(fn) + ": bad argument: " + what);
-        return -1;
-    };
-    if (!s) return bad("null scene");
-    if (!u) return bad("null uniforms");
-    if (!sum) return bad(device ? "null d_sum" : "null out_mean");
-    if (device && (reinterpret_cast<uintptr_t>(sum) % 16 != 0 || reinterpret_cast<uintptr_t>(sumsq) % 16 != 0))
-        return bad("d_sum and d_sumsq must be aligned to 16 bytes");
-    if (u->basicShading) return bad("basicShading: the preview has no tonemap, rt2_render gives its linear value");
-    if (u->numRaysPerPixel < 1) return bad("numRaysPerPixel must be >= 1");
-    if (u->width < 1 || u->height < 1) return bad("width and height must be >= 1");
-    *rows = rt2_shard_rows((int)u->height, sh);
-    if (*rows < 0) return bad("bad shard");
-    return 0;
-}
-
 extern "C" int rt2_render_linear(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count,
                                  rt2_shard sh, float* d_sum, float* d_sumsq, void* stream) {
     int rows = 0;
-    if (render_linear_args("rt2_render_linear", s, u, sh, d_sum, d_sumsq, true, &rows) != 0) return -1;
+    if (render_args({"rt2_render_linear", "d_sum", true, false}, s, u, sh, d_sum, d_sumsq, &rows) != 0) return -1;
     if (frame_count == 0 || rows == 0) return 0;
     return render_launch(s, u, frame_begin, frame_count, sh, d_sum, nullptr, d_sumsq, true, stream);
 }
@@ -1454,55 +1495,33 @@ extern "C" int rt2_resolve_tonemap(const float* d_linear_sum, int64_t n, uint32_
 extern "C" int rt2_render_linear_host(rt2_scene* s, const rt2_uniforms* u, uint32_t frame_begin, uint32_t frame_count,
                                       rt2_shard sh, float* out_mean, float* out_meansq) {
     int rows = 0;
-    if (render_linear_args("rt2_render_linear_host", s, u, sh, out_mean, out_meansq, false, &rows) != 0) return -1;
+    if (render_args({"rt2_render_linear_host", "out_mean", false, false}, s, u, sh, out_mean, out_meansq, &rows) != 0)
+        return -1;
     const size_t n = (size_t)rows * u->width;
     if (n == 0 || frame_count == 0) return 0;
-    HIPCHECK(hipSetDevice(s->device));
-    if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
-    hipStream_t st = s->host_stream;
-    if (n > s->lin_cap) {  // sums, second moments and their resolved means: grown together, freed with the scene
-        HIPCHECK(hipStreamSynchronize(st));
-        for (float4*& b : s->d_lin) {
-            (void)hipFree(b);
-            b = nullptr;
-        }
-        s->lin_cap = 0;
-        for (float4*& b : s->d_lin) HIPCHECK(hipMalloc(&b, n * sizeof(float4)));
-        s->lin_cap = n;
-    }
-    float4* const d_sum = s->d_lin[0];
-    float4* const d_sq = out_meansq ? s->d_lin[1] : nullptr;
-    HIPCHECK(hipMemsetAsync(d_sum, 0, n * sizeof(float4), st));
-    if (d_sq) HIPCHECK(hipMemsetAsync(d_sq, 0, n * sizeof(float4), st));
-    if (rt2_render_linear(s, u, frame_begin, frame_count, sh, reinterpret_cast<float*>(d_sum),
-                          reinterpret_cast<float*>(d_sq), st) != 0)
+    if (host_images(s, n, out_meansq != nullptr, n * sizeof(float4)) != 0) return -1;
+    if (rt2_render_linear(s, u, frame_begin, frame_count, sh, s->host_img[0].as<float>(),
+                          out_meansq ? s->host_img[1].as<float>() : nullptr, s->host_stream) != 0)
         return -1;
-    if (rt2_resolve_rgba32f(reinterpret_cast<const float*>(d_sum), (int64_t)n, frame_count,
-                            reinterpret_cast<float*>(s->d_lin[2]), st) != 0)
-        return -1;
-    HIPCHECK(hipMemcpyAsync(out_mean, s->d_lin[2], n * sizeof(float4), hipMemcpyDeviceToHost, st));
-    if (d_sq) {
-        if (rt2_resolve_rgba32f(reinterpret_cast<const float*>(d_sq), (int64_t)n, frame_count,
-                                reinterpret_cast<float*>(s->d_lin[3]), st) != 0)
-            return -1;
-        HIPCHECK(hipMemcpyAsync(out_meansq, s->d_lin[3], n * sizeof(float4), hipMemcpyDeviceToHost, st));
-    }
-    HIPCHECK(hipStreamSynchronize(st));  // only this render's stream, not the device
+    if (host_mean(s, 0, 2, n, frame_count, out_mean) != 0) return -1;
+    if (out_meansq && host_mean(s, 1, 3, n, frame_count, out_meansq) != 0) return -1;
+    HIPCHECK(hipStreamSynchronize(s->host_stream));  // only this render's stream, not the device
     return 0;
 }
 
 /* -------------------------------------------------------------------------
  * Ray queries (rt2_query.h, rt2_occluded.h, rt2_surface.h, rt2_shade.h, rt2_radiance.h)
  *
- * The five families share what is below (DESIGN.md "The query frame"): the argument check, the RenderParams fill,
- * launch_query and the blocking wrappers' staging; each entry point adds its options and its kernels.
+ * The five families share what is below (DESIGN.md "The query frame"): the argument check, launch_query and the
+ * blocking wrappers' staging, and with the renders scene_params, launch_begin and launch_end above; each entry point
+ * adds its options and its kernels.
  * ----------------------------------------------------------------------- */
 namespace {
 // trace_rays_k5r with the arithmetic of 353 (every group resident) and of 355
 // (38 groups resident, the rest read from L2: no structural limit at 256
 // groups, so it serves every larger scene in the filter's range too)
-constexpr MfmaSpec kQueryRes = kt_win(kt_res(false, false, true, 4), kResWin);
-constexpr MfmaSpec kQueryResL2 = kt_win(kt_res(true, false, true, 4), kResWin);
+constexpr MfmaSpec kQueryRes = kResFrame;
+constexpr MfmaSpec kQueryResL2 = kResL2;
 #ifdef RT2_EXPERIMENTS
 // A/B arms of the resident query kernel (rt2_scene_set_query_arm): 1 = its diagnostic counters and clocks (the
 // render's 350), 2 = the Y product in the first window too, which a caller's tmax can prune with (the render's 351)
@@ -1563,34 +1582,6 @@ int query_args(const char* who, const rt2_scene* s, int64_t n, int flags, bool d
     return 0;
 }
 
-// What every query's search reads.
-RenderParams query_params(const rt2_scene* s) {
-    RenderParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.tri = s->d_tri;
-    p.n_tris = s->n_tris;
-    p.mfma_A = s->mfma_A;
-    p.mfma_kt_frag = s->d_mfma_kt;
-    p.nodes = s->d_nodes;
-    p.stack_slots = s->bvh_depth + 2;
-    p.item_counter = s->d_counters;
-    p.seg_counter = s->d_counters + 1;
-    return p;
-}
-
-// ... and what surface_record, shade_step and radiance_step read of the materials and textures.
-void query_shading_params(const rt2_scene* s, RenderParams& p) {
-    p.unit_n = s->d_unit_n;
-    p.tri_mtl = s->d_mtl;
-    p.mats = s->d_mats;
-    p.n_mats = s->n_mats;
-    p.raw = s->d_raw;
-    p.texels = s->d_texels;
-    p.tex_desc = s->d_tex_desc;
-    p.n_tex = s->n_tex;
-    p.num_textures = std::min(s->n_tex, 5);  // a ray query has no uniforms: the images bound, at most the five units
-}
-
 // A family's resident or L2 kernel on `blocks` workgroups, and its scalar kernel on the rays of q.
 template <auto RES, auto RES_L2, class Q>
 void launch_k5r(bool resident, unsigned blocks, hipStream_t st, const RenderParams& p, const Q& q) {
@@ -1620,8 +1611,7 @@ int launch_query(rt2_scene* s, QueryFamily family, int64_t n, int flags, hipStre
                  Scalar scalar_k) {
     const bool bvh = s->traversal == RT2_TRAVERSAL_BVH;
     const bool matrix = !bvh && !(flags & RT2_TRACE_SCALAR) && s->mfma_ok;
-    // a query shares the scene's counters with its renders: the same order
-    if (s->last_launch_valid) HIPCHECK(hipStreamWaitEvent(st, s->last_launch, 0));
+    if (launch_begin(s, st) != 0) return -1;  // a query shares the scene's counters with its renders: the same order
     QueryForm form;
     if (matrix) {
         // one 16-wave workgroup per CU, and no more workgroups than have 1,024 rays each:
@@ -1640,24 +1630,7 @@ int launch_query(rt2_scene* s, QueryFamily family, int64_t n, int flags, hipStre
     }
     s->last_kind = matrix ? K_MFMA : bvh ? K_BVH : K_SMEM;
     s->last_variant = query_code(family, form);
-    if (!s->last_launch) HIPCHECK(hipEventCreateWithFlags(&s->last_launch, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(s->last_launch, st));
-    s->last_launch_valid = true;
-    s->tests_per_seg = (unsigned long long)s->n_tris;
-    return 0;
-}
-
-// Grows one of the scene's staging buffers to `bytes` (the stream is drained first: the old buffer may still be
-// in use).
-int staging_grow(rt2_scene* s, Staging& b, size_t bytes) {
-    if (bytes <= b.cap) return 0;
-    HIPCHECK(hipStreamSynchronize(s->host_stream));
-    (void)hipFree(b.ptr);
-    b.ptr = nullptr;
-    b.cap = 0;
-    HIPCHECK(hipMalloc(&b.ptr, bytes));
-    b.cap = bytes;
-    return 0;
+    return launch_end(s, st);
 }
 
 // The blocking wrappers' start: the scene's device, host_stream, and staging for n rays, n stream words when
@@ -1665,9 +1638,9 @@ int staging_grow(rt2_scene* s, Staging& b, size_t bytes) {
 int staging_begin(rt2_scene* s, size_t n, bool rng, size_t out_bytes) {
     HIPCHECK(hipSetDevice(s->device));
     if (!s->host_stream) HIPCHECK(hipStreamCreateWithFlags(&s->host_stream, hipStreamNonBlocking));
-    if (staging_grow(s, s->stage_rays, n * sizeof(rt2_ray)) != 0) return -1;
-    if (rng && staging_grow(s, s->stage_rng, n * sizeof(uint32_t)) != 0) return -1;
-    return staging_grow(s, s->stage_out, out_bytes);
+    if (staging_grow(s->stage_rays, n * sizeof(rt2_ray), &s->host_stream) != 0) return -1;
+    if (rng && staging_grow(s->stage_rng, n * sizeof(uint32_t), &s->host_stream) != 0) return -1;
+    return staging_grow(s->stage_out, out_bytes, &s->host_stream);
 }
 
 // A blocking ray-array query over host arrays: rays (and the streams, when rng) in, query(d_rays, d_rng, d_out,
@@ -1728,7 +1701,7 @@ extern "C" int rt2_trace_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, rt
     if (n == 0) return 0;
     HIPCHECK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    const RenderParams p = query_params(s);
+    const RenderParams p = scene_params(s);
     const QueryParams q{d_rays, d_hits, (long long)n};
     return launch_query(
         s, QF_CLOSEST, n, flags, st,
@@ -1764,7 +1737,7 @@ extern "C" int rt2_occluded(rt2_scene* s, const rt2_ray* d_rays, int64_t n, uint
     if (n == 0) return 0;
     HIPCHECK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    const RenderParams p = query_params(s);
+    const RenderParams p = scene_params(s);
     const OccParams q{d_rays, d_occluded, (long long)n};
     return launch_query(
         s, QF_OCCLUDED, n, flags, st,
@@ -1812,8 +1785,8 @@ extern "C" int rt2_surface_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, 
     if (n == 0) return 0;
     HIPCHECK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    RenderParams p = query_params(s);
-    query_shading_params(s, p);
+    RenderParams p = scene_params(s);
+    scene_shading_params(s, p);
     const SurfaceParams q{d_rays, d_out, (long long)n};
     return launch_query(
         s, QF_SURFACE, n, flags, st,
@@ -1843,8 +1816,8 @@ extern "C" int rt2_shade_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n, co
     if (n == 0) return 0;
     HIPCHECK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    RenderParams p = query_params(s);
-    query_shading_params(s, p);
+    RenderParams p = scene_params(s);
+    scene_shading_params(s, p);
     p.maxBounce = opts->max_bounce;
     p.basicShadow = opts->shadow;
     p.light[0] = opts->light[0];
@@ -1882,8 +1855,8 @@ extern "C" int rt2_radiance_rays(rt2_scene* s, const rt2_ray* d_rays, int64_t n,
     if (n == 0) return 0;
     HIPCHECK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
-    RenderParams p = query_params(s);
-    query_shading_params(s, p);
+    RenderParams p = scene_params(s);
+    scene_shading_params(s, p);
     p.maxBounce = opts->max_bounce;
     p.envLight = opts->environmental_light;
     const RadianceParams q{d_rays, d_rng, d_out, (long long)n};
@@ -1949,12 +1922,6 @@ int path_rays_args(const char* who, const rt2_scene* s, const rt2_uniforms* u, r
         return -1;
     }
     return 0;
-}
-
-void copy3(float* d, const rt2_vec4& v) {
-    d[0] = v.x;
-    d[1] = v.y;
-    d[2] = v.z;
 }
 
 // What CameraParams and PathRaysParams share: the view, the image and shard, the slab.
@@ -2052,11 +2019,11 @@ extern "C" int rt2_scene_diag_ex(rt2_scene* s, unsigned long long* out, int n) {
 // pixels it describes (0 = no valid map), < 0 on error.
 extern "C" long long rt2_scene_cost_map(rt2_scene* s, uint32_t* out, unsigned long long n) {
     if (!s) return -1;
-    if (!s->d_cost || s->cost_npix == 0) return 0;
+    if (!s->cost.ptr || s->cost_npix == 0) return 0;
     if (out && n >= s->cost_npix) {
         HIPCHECK(hipSetDevice(s->device));
         HIPCHECK(hipDeviceSynchronize());
-        HIPCHECK(hipMemcpy(out, s->d_cost, s->cost_npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(out, s->cost.ptr, s->cost_npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     return (long long)s->cost_npix;
 }
