@@ -103,6 +103,13 @@
 // the lower index on equal distances, which leaves the index-order scan's
 // result, and the hit's slot is mapped to its index after the sweep (DESIGN.md
 // "Slot order").
+//
+// MfmaSpec::exact_spread (353, 354): per round of the episode every lane tests
+// its first pair itself, and the pairs that are left are dealt out one per
+// lane through a list in the wave's second unused T1 piece and merged by a
+// 64-bit minimum (exact_spread_scan, exact_window_lanes; DESIGN.md "Leftover
+// pairs on all lanes").  The result is the minimum by (distance, index) over
+// the same accepted pairs.
 #pragma once
 
 // v_writelane_b32 (value and lane wave-uniform).  clang has a builtin for
@@ -164,6 +171,42 @@ __device__ __forceinline__ void xl_counts(MfmaDiag& dg, int pairs, int k, int ro
 __host__ __device__ constexpr int xl_row_of_bit(int b) { return 8 * ((b & 15) >> 2) + 4 * (b >> 4) + (b & 3); }
 __host__ __device__ constexpr int xl_bit_of_row(int r) { return 16 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3); }
 
+// MfmaSpec::exact_spread (353, 354): a round's leftover pairs on all lanes.
+// exact_window_lanes' per-lane loop runs until the wave's busiest ray is done,
+// and after every lane's first pair the pairs that are left sit on a few
+// lanes.  So per round: every lane tests its first pair itself; the r pairs a
+// lane has left get the places at .. at + r - 1 (exclusive prefix sum over the
+// wave, total Rw) of a list in LDS, an entry being (lane, bit of its mask);
+// lane w < Rw tests entry w on a copy of the source ray's o, d and (best, bi)
+// as they are after the first pair, the unchanged mt_quantities / mt_pass3 /
+// mt_exact_slot; a worker whose copy improved publishes distance bits << 32 |
+// triangle index << 16 | slot by an unsigned 64-bit minimum into the source
+// lane's slot, and the source takes its slot's key.  The image cannot change
+// (DESIGN.md "Leftover pairs on all lanes"): a ray's result is the minimum by
+// (distance, index) over its accepted pairs; a worker's bound is looser than
+// the scan's and passes every pair the scan passes; accepted distances are
+// above 1e-6, so their bits order as unsigned integers; the minimum does not
+// depend on the order.  A round with no lane holding two leftovers (the loop
+// would end after one more trip) or with Rw > 64 takes the per-lane loop.
+// Inclusive DPP scan (row_shr 1, 2, 4, 8 inside a row of 16, then row_bcast
+// 15 / 31 across the rows); returns Rw, the count on the lanes below in `at`.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int dpp_add_step(int x) {
+    // lanes without a source, and rows outside ROW_MASK, add `old` = 0
+    return x + __builtin_amdgcn_update_dpp(0, x, CTRL, ROW_MASK, 0xf, false);
+}
+__device__ __forceinline__ int exact_spread_scan(int r, int& at) {
+    int x = r;
+    x = dpp_add_step<0x111, 0xf>(x);  // row_shr:1
+    x = dpp_add_step<0x112, 0xf>(x);  // row_shr:2
+    x = dpp_add_step<0x114, 0xf>(x);  // row_shr:4
+    x = dpp_add_step<0x118, 0xf>(x);  // row_shr:8
+    x = dpp_add_step<0x142, 0xa>(x);  // row_bcast:15 into rows 1, 3
+    x = dpp_add_step<0x143, 0xc>(x);  // row_bcast:31 into rows 2, 3
+    at = x - r;
+    return __builtin_amdgcn_readlane(x, 63);
+}
+
 // The exact episode of one window with the tests per ray (MfmaSpec::
 // exact_lanes) instead of per wave.  exact_window runs every hot triangle's
 // test on all 64 lanes, though only a few rays asked for it.  Here:
@@ -199,8 +242,20 @@ template <MfmaSpec S, bool YP, bool LDS, class Rebuild>
 __device__ __forceinline__ void exact_window_lanes(int maskv, int Gw, bool more, int n_tris, const float4* tri4,
                                                    const h8* a0, const h8* y1, const h8* recs, bool upper, const f3& o,
                                                    const f3& d, float& best, int& bi, float& bestK, MfmaDiag& dg,
-                                                   Rebuild rebuild, [[maybe_unused]] const int* slot_tri = nullptr) {
+                                                   Rebuild rebuild, [[maybe_unused]] const int* slot_tri = nullptr,
+                                                   [[maybe_unused]] unsigned long long* xs_diag = nullptr,
+                                                   [[maybe_unused]] int xs_wave = 0) {
     const int lane = (int)lane_id();
+    // MfmaSpec::exact_spread: the wave's list (64 x 4 B) and merge slots (64 x 8 B at byte 512) in the T1 piece of
+    // group 16 + wave, which nothing else reads or writes (render_mfma_k5r's static_assert)
+    [[maybe_unused]] uint32_t* xs_list = nullptr;
+    [[maybe_unused]] unsigned long long* xs_slot = nullptr;
+    // (the kernel's one resident window, which has no Y; the other forms are never run in such a kernel)
+    constexpr bool XS = S.exact_spread && LDS && !YP;
+    if constexpr (XS) {
+        xs_list = reinterpret_cast<uint32_t*>(const_cast<h8*>(recs) + (4 * (16 + xs_wave) + 3) * 64);
+        xs_slot = reinterpret_cast<unsigned long long*>(xs_list + 128);
+    }
     [[maybe_unused]] unsigned long long tc = 0;
     if constexpr (S.diag) {
         dg.claims += 1;
@@ -310,13 +365,107 @@ __device__ __forceinline__ void exact_window_lanes(int maskv, int Gw, bool more,
         };
         Tri ta, tb2;
         fetch(ta);
-        // two steps per trip, the two triangles' registers changing roles (no copies, and no wait for the
-        // requested triangle before the trip's end)
+        if constexpr (XS) {
+            // MfmaSpec::exact_spread (the comment above exact_spread_scan): every lane's first pair on its own
+            // lane, against its current bound
+            {
+                if constexpr (S.diag) iters += 1;
+                const bool has = pm != 0;
+                pm &= pm - 1;
+                if (has) {
+                    const MtQ qq = mt_quantities(o, d, ta.t0, ta.t1, ta.t2);
+                    if (mt_pass3(qq, bestK)) {
+                        if constexpr (S.slot_order)
+                            mt_exact_slot(qq, ta.idx, slot_tri, best, bi, bestK);
+                        else
+                            mt_exact(qq, ta.idx, best, bi, bestK);
+                    }
+                }
+            }
+            // the leftovers: r per lane, `at` of them on the lanes below, Rw in the wave
+            const int r = __popc(pm);
+            int at;
+            const int Rw = exact_spread_scan(r, at);
+            if (Rw) {
+                const bool spread = Rw <= 64 && __ballot(r >= 2) != 0;
+                if constexpr (S.diag) {
+                    xs_diag[0] += (unsigned long long)Rw;
+                    xs_diag[1] += spread ? 1ull : Rw > 64 ? 1ull << 40 : 0ull;
+                }
+                if (spread) {
+                    // scatter: entry at + j = this lane and its j-th remaining bit; the merge slot empty
+                    // (the lane number from here on: an address formed outside the branch would hold a register
+                    // across the products)
+                    int wl = lane;
+                    asm volatile("" : "+v"(wl));
+                    xs_slot[wl] = ~0ull;
+                    while (pm) {
+                        xs_list[at++] = (uint32_t)lane | (uint32_t)__builtin_ctz(pm) << 8;
+                        pm &= pm - 1;
+                    }
+                    asm volatile("" ::: "memory");  // the wave's LDS operations keep their order
+                    // worker trip: lane w < Rw takes entry w (the other lanes entry "lane 0, bit 0", unused)
+                    const bool work = lane < Rw - (S.spread_drop ? 1 : 0);
+                    const uint32_t e = work ? xs_list[wl] : 0u;
+                    const int from = 4 * (int)(e & 63u);
+                    Tri tw;
+                    tw.idx = __builtin_amdgcn_ds_bpermute(4 * (int)(e >> 8 & 31u), lst);
+                    tw.t0 = tri4[3 * tw.idx], tw.t1 = tri4[3 * tw.idx + 1], tw.t2 = tri4[3 * tw.idx + 2];
+                    int wtri = tw.idx;  // the pair's triangle index, the key's tie break
+                    if constexpr (S.slot_order) wtri = slot_tri[tw.idx];
+                    auto pull = [&](float v) {  // lane `from`'s value (ds_bpermute)
+                        return __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(v)));
+                    };
+                    const f3 so = mk(pull(o.x), pull(o.y), pull(o.z));
+                    const f3 sd = mk(pull(d.x), pull(d.y), pull(d.z));
+                    float cbest = pull(best);
+                    int cbi = __builtin_amdgcn_ds_bpermute(from, bi);
+                    float cbestK = cbest * 1.0009765625f;  // as mt_exact sets it (and as the sweep starts it)
+                    if (work) {
+                        const MtQ qq = mt_quantities(so, sd, tw.t0, tw.t1, tw.t2);
+                        if (mt_pass3(qq, cbestK)) {
+                            if constexpr (S.slot_order)
+                                mt_exact_slot(qq, tw.idx, slot_tri, cbest, cbi, cbestK);
+                            else
+                                mt_exact(qq, tw.idx, cbest, cbi, cbestK);
+                            // improved on the source's (best, bi): publish (distance, index | slot)
+                            if (cbi == tw.idx) {
+                                const uint32_t lo = S.slot_order ? (uint32_t)wtri << 16 | (uint32_t)tw.idx
+                                                                 : (uint32_t)tw.idx;
+                                __hip_atomic_fetch_min(&xs_slot[e & 63u],
+                                                       (unsigned long long)__float_as_uint(cbest) << 32 | lo,
+                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                            }
+                        }
+                    }
+                    asm volatile("" ::: "memory");
+                    // merge: every published key is below the lane's own (best, index), so is their minimum
+                    const unsigned long long key = xs_slot[wl];
+                    if (key != ~0ull) {
+                        best = __uint_as_float((uint32_t)(key >> 32));
+                        bi = (int)((uint32_t)key & (S.slot_order ? 0xffffu : ~0u));
+                        bestK = best * 1.0009765625f;
+                    }
+                } else {
+                    // too few leftovers to gain, or more than the wave has lanes: the per-lane loop
+                    fetch(ta);
 #pragma nounroll
-        while (__ballot(pm != 0)) {
-            step(ta, tb2);
-            if (!__ballot(pm != 0)) break;
-            step(tb2, ta);
+                    while (__ballot(pm != 0)) {
+                        step(ta, tb2);
+                        if (!__ballot(pm != 0)) break;
+                        step(tb2, ta);
+                    }
+                }
+            }
+        } else {
+            // two steps per trip, the two triangles' registers changing roles (no copies, and no wait for the
+            // requested triangle before the trip's end)
+#pragma nounroll
+            while (__ballot(pm != 0)) {
+                step(ta, tb2);
+                if (!__ballot(pm != 0)) break;
+                step(tb2, ta);
+            }
         }
         if (c < 32) break;
     }
@@ -538,7 +687,9 @@ __device__ __forceinline__ SlotImage slot_image(const RenderParams& p) {
 template <MfmaSpec S>
 __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* rec, const f3& o, const f3& d,
                                              float& best, int& bi, float& bestK, MfmaDiag& dg, bool upper,
-                                             unsigned long long act = 0, ClusterDiag* cd = nullptr) {
+                                             unsigned long long act = 0, ClusterDiag* cd = nullptr,
+                                             [[maybe_unused]] unsigned long long* xs_diag = nullptr,
+                                             [[maybe_unused]] int xs_wave = 0) {
     const int lane = (int)lane_id();
     // MfmaSpec::diag: shader clocks of the ray setup (t_wait), the products
     // with their record reads (t_filt), the exact phase with the Y rebuilds
@@ -832,7 +983,7 @@ __device__ __forceinline__ bool sweep_kt_res(const RenderParams& p, const h8* re
                     // a first window is resident; the L2 loop's windows gather from the scene's records
                     if (!YP || resident)
                         exact_window_lanes<S, YP, true>(maskv, Gw, more, n_tris, tri4, a0, y1, rec, upper, o, d, best,
-                                                        bi, bestK, dg, rebuild, slot_tri);
+                                                        bi, bestK, dg, rebuild, slot_tri, xs_diag, xs_wave);
                     else if constexpr (YP)
                         exact_window_lanes<S, YP, false>(maskv, Gw, more, n_tris, tri4, a0, y1,
                                                          reinterpret_cast<const h8*>(p.mfma_kt_frag), upper, o, d, best,
@@ -942,7 +1093,22 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
     [[maybe_unused]] std::conditional_t<S.cluster_rows8, ClusterDiag8,
                                         std::conditional_t<S.cluster_rows, ClusterDiag, NoClusterDiag>> cdg;
     [[maybe_unused]] PathDiagSlot<S.diag> pds;
+    // MfmaSpec::exact_spread, diag: [0] the rounds' leftover pairs (Rw) summed, [1] rounds that took the spread
+    // path, + 2^40 per round that fell back because Rw > 64
+    struct SpreadDiag {
+        unsigned long long n[2] = {};
+    };
+    [[maybe_unused]] std::conditional_t<S.exact_spread && S.diag, SpreadDiag, NoClusterDiag> xsd;
+    if constexpr (S.exact_spread) {
+        // exact_window_lanes keeps wave w's list and merge slots in the T1 piece of group 16 + w: behind cam_park's
+        // pieces (groups 0 .. NW - 1), never loaded, no LDS added, no other wave touches it, no barrier
+        constexpr bool no_t1 = !S.y_first && S.exact_win >= kResGroups && !S.res_l2;
+        static_assert(no_t1 && NW <= 16 && 2 * NW <= kResGroups && S.exact_lanes,
+                      "exact_spread works in T1 pieces that nothing else uses");
+    }
     const int wave = (int)(threadIdx.x >> 6);
+    [[maybe_unused]] int xs_wave = 0;  // MfmaSpec::exact_spread: the wave's number in a scalar register
+    if constexpr (S.exact_spread) xs_wave = __builtin_amdgcn_readfirstlane(wave);
     // MfmaSpec::lean: the wave counts its lanes' segments (no per-lane counter)
     [[maybe_unused]] unsigned long long segs_w = 0;
     // diag wave timeline (p.wave_log, 10 words per wave: start, first lane out
@@ -1058,7 +1224,11 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
         int bi = -1;
         phase_prio<S>(0);
         bool swept;
-        if constexpr (S.cluster_rows)
+        if constexpr (S.exact_spread && S.diag)
+            swept = sweep_kt_res<S>(p, rs.rec, ro, rd, best, bi, bestK, dg, upper, act, &cdg, xsd.n, xs_wave);
+        else if constexpr (S.exact_spread)
+            swept = sweep_kt_res<S>(p, rs.rec, ro, rd, best, bi, bestK, dg, upper, act, &cdg, nullptr, xs_wave);
+        else if constexpr (S.cluster_rows)
             swept = sweep_kt_res<S>(p, rs.rec, ro, rd, best, bi, bestK, dg, upper, act, &cdg);
         else
             swept = sweep_kt_res<S>(p, rs.rec, ro, rd, best, bi, bestK, dg, upper);
@@ -1138,6 +1308,12 @@ __global__ __launch_bounds__(S.block) __attribute__((amdgpu_waves_per_eu(S.waves
                 atomicAdd(p.seg_counter + 28, cdg.r16);      // ... at most 16 rays need it (and at least one)
                 // (slot 29 is the scene's scratch word for the record preparation's flags)
                 if constexpr (S.cluster_rows8) atomicAdd(p.seg_counter + 30, cdg.r8);  // ... at most 8 (and at least one)
+            }
+            if constexpr (S.exact_spread) {  // SpreadDiag: per round of an episode
+                atomicAdd(p.seg_counter + 4, xsd.n[0]);   // ... the pairs left after every lane's first (Rw), summed
+                // (two counts in one word: 4 and 11 are this kernel's only free slots; 5 and 6 are preset per render,
+                // 29 and 30 taken)
+                atomicAdd(p.seg_counter + 11, xsd.n[1]);  // ... spread rounds, + 2^40 per fallback with Rw > 64
             }
         }
 }

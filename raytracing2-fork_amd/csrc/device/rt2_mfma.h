@@ -89,6 +89,12 @@ struct MfmaSpec {
                               // breaks distance ties by the triangles' indices and the sweep returns an index
                               // (rt2_k5_resident.h slot_image; DESIGN.md "Slot order")
     bool linear = false;  // the linear sink (rt2_render_linear; rt2_path.h end_path_linear)
+    bool exact_spread = false;  // with exact_lanes in a kernel without the T1 pieces: after every lane's first pair of
+                                // a round, the pairs that are left are dealt out one per lane through a list in LDS
+                                // and merged by a 64-bit minimum (rt2_k5_resident.h exact_spread_scan; DESIGN.md
+                                // "Leftover pairs on all lanes")
+    bool spread_drop = false;   // with exact_spread, one experiment arm (the tests' negative control): a spread round's
+                                // last list entry is not tested
 };
 
 // per-wave diagnostic counts (wave-uniform; MfmaSpec::diag)

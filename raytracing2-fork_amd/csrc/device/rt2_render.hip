@@ -706,6 +706,12 @@ constexpr MfmaSpec kt_slot(MfmaSpec x) {
     x.slot_order = true;
     return x;
 }
+// ... its rounds' leftover pairs dealt out over all lanes (MfmaSpec::exact_spread; DESIGN.md "Leftover pairs on all
+// lanes")
+constexpr MfmaSpec kt_spread(MfmaSpec x) {
+    x.exact_spread = true;
+    return x;
+}
 constexpr int kResWin = 38;  // the window of 353-356 (and the diagnostic 350): the whole resident sweep, then one episode
 constexpr int kResL2Groups = 256;  // render_mfma_k5r with res_l2: kResGroups groups resident, the rest from L2
 // records streamed through LDS tiles (rt2_k5_tiles.h): 19-group tiles, each ray's own W, issue priority by
@@ -725,7 +731,9 @@ constexpr MfmaSpec kt_tiles_flow4() {
 // frame of 353 before its per-ray, pair-loop, cluster and slot pieces, and 355's as it is (kQueryRes, kQueryResL2).
 constexpr MfmaSpec kResFrame = kt_win(kt_res(false, false, true, 4), kResWin);
 constexpr MfmaSpec kResSlabFrame = kt_win(kt_res(false, true, true), kResWin);
-constexpr MfmaSpec kt_product(MfmaSpec frame) { return kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(frame)))))); }
+constexpr MfmaSpec kt_product(MfmaSpec frame) {
+    return kt_spread(kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(frame)))))));
+}
 constexpr MfmaSpec kRes = kt_product(kResFrame);
 constexpr MfmaSpec kResSlab = kt_product(kResSlabFrame);
 constexpr MfmaSpec kResL2 = kt_win(kt_res(true, false, true, 4), kResWin);
@@ -764,7 +772,8 @@ constexpr Variant kVariants[] = {
     // (DESIGN.md "Two groups per loop trip") and keep each pixel's camera end point in LDS instead of recomputing it
     // per ray (DESIGN.md "The camera end point once per pixel")
     // and sweep the scene's slot image (DESIGN.md "Slot order"), a compact cluster that at most 8 rays need with 8-row
-    // products (DESIGN.md "8-row products")
+    // products (DESIGN.md "8-row products"), and deal a round's leftover exact pairs out over all 64 lanes (DESIGN.md
+    // "Leftover pairs on all lanes")
     RT2_PRODUCT(353, K_MFMA, render_mfma_k5r, kRes, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4", kResGroups, true),
     RT2_PRODUCT(354, K_MFMA, render_mfma_k5r, kResSlab, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw", kResGroups, true),
     RT2_PRODUCT(355, K_MFMA, render_mfma_k5r, kResL2, 1024, "mfmarl2/1024/kt4/res38l2/coop4/w4/cmp/dpp/lean/lw/pp4", kResL2Groups),
@@ -836,6 +845,13 @@ constexpr Variant kVariants[] = {
     RT2_VARIANT(417, K_MFMA, render_mfma_k5r<kt_slot(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 4), kResWin))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/r16", kResGroups, true),
     RT2_VARIANT(418, K_MFMA, render_mfma_k5r<kt_slot(kt_cr16(kt_park(kt_pair(kt_xl(kt_win(kt_res(false, true, true), kResWin))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/r16", kResGroups, true),
     RT2_VARIANT(419, K_MFMA, render_mfma_k5r<kt_slot(kt_cr8(kt_cr16(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 0, true), kResWin))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/xl/cr8/slot", kResGroups, true),
+    // a round's leftover pairs on all lanes (MfmaSpec::exact_spread; 353 / 354 take it): 353's and 354's specs with the
+    // per-lane loop alone (loop: the form before), 419's counters with the spread path and its three, and the tests'
+    // negative control (drop: a spread round's last list entry is not tested; its image is wrong on purpose)
+    RT2_VARIANT(420, K_MFMA, render_mfma_k5r<kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(kResFrame))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/loop", kResGroups, true),
+    RT2_VARIANT(421, K_MFMA, render_mfma_k5r<kt_slot(kt_cr8(kt_cr16(kt_park(kt_pair(kt_xl(kResSlabFrame))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/fair/dpp/lean/lw/loop", kResGroups, true),
+    RT2_VARIANT(422, K_MFMA, render_mfma_k5r<kt_spread(kt_slot(kt_cr8(kt_cr16(kt_pair(kt_xl(kt_win(kt_res(false, false, true, 0, true), kResWin)))))))>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/diag/dpp/lean/lw/xl/cr8/slot/spread", kResGroups, true),
+    RT2_VARIANT(423, K_MFMA, render_mfma_k5r<[] { MfmaSpec x = kRes; x.spread_drop = true; return x; }()>, 1024, "mfmar/1024/kt4/res38/coop4/w4/cmp/dpp/lean/lw/pp4/drop", kResGroups, true),
     // the tile stream at 3 waves per SIMD (380 takes 4 with the lean lane state): with its diagnostic clocks; without
     // flow_prio; with the lean lane state
     RT2_VARIANT(370, K_MFMA, render_mfma_k5t<kt_tiles_flow()>, 768, "mfmat5/768/kt4/tile19/coop0/w3/cmp/regs/perm/lw/flowp"),

@@ -6,7 +6,7 @@ phase) and how many (wave, triangle) exact tests follow; for the resident
 kernel also its phase clocks and, per exact episode, the (ray, triangle) pairs,
 the busiest ray's pairs and the rounds of 32 hot triangles (350: counted on
 the exact quantities; 402, the per-ray episode MfmaSpec::exact_lanes: what
-it ran)."""
+it ran; 422, MfmaSpec::exact_spread: the rounds' leftover pairs)."""
 import argparse
 import ctypes as C
 import json
@@ -102,6 +102,16 @@ for v in [int(x) for x in a.variants.split(",")]:
                            pairs_per_hot_triangle=round(pairs / max(exact, 1), 2),
                            k_per_episode=round(ksum / max(episodes, 1), 2), k_max=kmax,
                            rounds_per_episode=round(rounds / max(episodes, 1), 3)))
+        # SpreadDiag (MfmaSpec::exact_spread diag: 422): per round of an episode, the pairs left after every lane's first
+        # (Rw), the rounds that dealt them out over the wave, and those that fell back on Rw > 64; the rest of the
+        # rounds had no leftover, or no lane with two
+        left, packed = c[5], c[12]
+        if rounds and (left or packed):
+            sp, big = packed & ((1 << 40) - 1), packed >> 40
+            res[name_of(v)].update(
+                spread=dict(leftovers_per_round=round(left / rounds, 2), leftovers_per_spread_round=round(left / max(sp, 1), 2),
+                            spread_round_share=round(sp / rounds, 4), over_64_round_share=round(big / rounds, 6),
+                            other_round_share=round(1 - (sp + big) / rounds, 4)))
 vs = list(imgs)
 res["bit_identical"] = all(bool((imgs[v] == imgs[vs[0]]).all()) for v in vs[1:])
 print(json.dumps(res, indent=1))
