@@ -543,6 +543,19 @@ int rt2_path_rays_host(rt2_scene* scene, const rt2_uniforms* uniforms, rt2_shard
  * accumulator for that frame.  Asynchronous; in place (d_out == d_linear_sum)
  * is allowed.  Bad arguments as rt2_resolve_rgba32f (a null pointer,
  * n_pixels < 0, frames == 0).
+ * A sum no render produces (a denoiser's output, say) gets what the formula
+ * gives in binary32, x = sum / frames, aces1(x) = clamp((x (2.51 x + 0.03)) /
+ * (x (2.43 x + 0.59) + 0.14), 0, 1) with a clamp that ignores a NaN operand:
+ *   - NaN, +inf and -inf give 0 (the quotient is NaN, and clamp(NaN) = 0);
+ *   - x up to 1.1643e19, where x (2.51 x + 0.03) overflows, gives 1 (1e6 does),
+ *     and so does x up to 1.1834e19, where inf / finite = inf clamps to 1;
+ *     from there on both products overflow, inf / inf = NaN, and the result is
+ *     0 — as for |x| beyond it on the negative side;
+ *   - a negative x follows the rational, whose denominator never vanishes:
+ *     -0.01195 < x <= -0 gives 0, below that the value is positive again and
+ *     reaches 1 at x = -0.2418 (x = -5 gives 1).
+ * A caller who wants another answer for such values clamps them first.
+ * (tests/test_gpu_numerics.py, tests/test_numerics_cases.py.)
  * ---------------------------------------------------------------------- */
 int rt2_render_linear(rt2_scene* scene, const rt2_uniforms* uniforms, uint32_t frame_begin, uint32_t frame_count,
                       rt2_shard shard, float* d_sum, float* d_sumsq, void* stream);

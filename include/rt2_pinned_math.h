@@ -30,7 +30,12 @@
 #define RT2PM_FN static inline
 #endif
 
+/* The fused multiply-add of every Horner step.  A build may supply its own
+ * (tests/test_numerics_cases.py compiles the oracle with an unfused one, to
+ * show that its inputs tell the two apart); the product never does. */
+#ifndef RT2PM_FMA
 #define RT2PM_FMA(a, b, c) __builtin_fmaf((a), (b), (c))
+#endif
 
 RT2PM_FN uint32_t rt2pm_f2u(float f) {
     union { float f; uint32_t u; } v;
@@ -41,6 +46,36 @@ RT2PM_FN float rt2pm_u2f(uint32_t u) {
     union { float f; uint32_t u; } v;
     v.u = u;
     return v.f;
+}
+
+/* min/max of the render path (clamp, smoothstep, the sky's clamp, aces1, the
+ * Russian-roulette p of trace(), normalizeColor): IEEE 754-2019
+ * minimumNumber / maximumNumber.  A NaN operand is ignored (two NaNs give NaN),
+ * and -0 < +0, so max(+0, -0) = max(-0, +0) = +0 and min of the two is -0,
+ * whatever the order.  C leaves the zeros' order to the library (x86's maxss
+ * returns its second operand), and GLSL 4.30's `y if x < y else x` returns the
+ * first; p is a divisor in trace(), so the case is pinned here.  On gfx950
+ * fmaxf/fminf compile to v_max_f32 / v_min_f32, which are this definition
+ * (tests/test_gpu_numerics.py holds the device to the explicit host form). */
+RT2PM_FN float rt2pm_fmaxf(float x, float y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fmaxf(x, y);
+#else
+    if (x != x) return y;
+    if (y != y) return x;
+    if (x == y) return rt2pm_u2f(rt2pm_f2u(x) & rt2pm_f2u(y)); /* +0 unless both are -0 */
+    return x < y ? y : x;
+#endif
+}
+RT2PM_FN float rt2pm_fminf(float x, float y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fminf(x, y);
+#else
+    if (x != x) return y;
+    if (y != y) return x;
+    if (x == y) return rt2pm_u2f(rt2pm_f2u(x) | rt2pm_f2u(y)); /* -0 if either is -0 */
+    return y < x ? y : x;
+#endif
 }
 
 /* 2^k for -126 <= k <= 127, exact. */
@@ -155,7 +190,12 @@ RT2PM_FN float rt2pm_cos_poly(float x) {
     return y + 1.0f;
 }
 
-/* Cody-Waite reduction by pi/4 (Cephes DP1..DP3); valid for |x| < 8192. */
+/* Cody-Waite reduction by pi/4 (Cephes DP1..DP3); accurate for |x| < 8192
+ * (the shader passes a few radians at most).  Beyond that the error grows with
+ * |x|, but host and device still agree in every bit while |x| * 4/pi < 2^31.
+ * From there on the (int) conversion is out of range (x86 gives INT_MIN, the
+ * GPU saturates) and rt2pm_sinf / rt2pm_cosf are undefined: no caller may
+ * pass such an argument, and no test compares one. */
 RT2PM_FN float rt2pm_reduce(float ax, int* quadrant) {
     int j = (int)(ax * 1.27323954473516f);
     float y = (float)j;

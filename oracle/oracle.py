@@ -73,15 +73,15 @@ def _load() -> C.CDLL:
     if not os.path.exists(LIB):
         build()
     L = C.CDLL(LIB)
-    if not hasattr(L, "oracle_closest_hits"):
+    if not hasattr(L, "oracle_numerics"):
         import _ctypes
         handle = L._handle
         del L
         _ctypes.dlclose(handle)  # unmapped before the file is replaced and loaded again
         build(force=True)
         L = C.CDLL(LIB)
-        if not hasattr(L, "oracle_closest_hits"):
-            raise RuntimeError(f"{LIB} lacks oracle_closest_hits after a rebuild")
+        if not hasattr(L, "oracle_numerics"):
+            raise RuntimeError(f"{LIB} lacks oracle_numerics after a rebuild")
     return L
 
 
@@ -120,6 +120,8 @@ def _declare(L: C.CDLL) -> C.CDLL:
     L.oracle_tonemap_srgb.argtypes = [C.c_float]
     L.oracle_pinned.restype = C.c_float
     L.oracle_pinned.argtypes = [C.c_int, C.c_float]
+    L.oracle_numerics.restype = C.c_int
+    L.oracle_numerics.argtypes = [C.c_int32, P, C.c_int64, P]
     return L
 
 
@@ -237,3 +239,25 @@ def pcg_sequence(seed: int, n: int):
 
 def pinned(which: int, x: float) -> float:
     return lib().oracle_pinned(which, x)
+
+
+# oracle_numerics' operation codes (rt_oracle.h); the product's rt2.NUMERICS_OPS is the same table.
+NUMERICS_OPS = {name: code for code, name in enumerate((
+    "div", "rcp", "sqrt", "fma", "mul", "add", "sub", "fmin", "fmax", "clamp", "dot", "cross", "length",
+    "normalize", "reflect", "refract", "mix", "smoothstep", "exp", "log", "acos", "cos", "sin", "pow", "aces1",
+    "srgb1", "sky", "rnd", "rnd_dir"))}
+
+
+def numerics(op, rows: np.ndarray, library: C.CDLL | None = None) -> np.ndarray:
+    """One operation of DESIGN.md §Numerics by the oracle's own functions: rows is (n, 9) uint32 bit patterns
+    (fewer columns are padded with zeros), the result (n, 4) uint32.  library: as for render()."""
+    code = NUMERICS_OPS[op] if isinstance(op, str) else int(op)
+    rows = np.asarray(rows, dtype=np.uint32)
+    assert rows.ndim == 2 and rows.shape[1] <= 9
+    full = np.zeros((len(rows), 9), np.uint32)
+    full[:, :rows.shape[1]] = rows
+    out = np.zeros((len(rows), 4), np.uint32)
+    rc = (library or lib()).oracle_numerics(code, full.ctypes.data, len(full), out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle_numerics failed: {rc}")
+    return out

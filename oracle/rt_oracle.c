@@ -15,6 +15,8 @@
  *                   fma(a.x,b.y,-(a.y*b.x)));
  *   - normalize(v) = v / sqrt(dot(v,v)) (GLSL 4.30 §8.5 definition), IEEE
  *     correctly-rounded / and sqrt;
+ *   - min/max (clamp, smoothstep, the Russian-roulette p) = rt2pm_fminf /
+ *     rt2pm_fmaxf: a NaN operand ignored, -0 < +0;
  *   - cos/sin/acos/exp/pow = include/rt2_pinned_math.h.
  * The GLSL driver the reference ran on is unknown (SURVEY.md §8c "Pins"), so
  * this file, not a GLSL run, is the definition the HIP kernel is held to.
@@ -62,7 +64,7 @@ static inline v3 mixs(v3 x, v3 y, float a) { return add(muls(x, 1.0f - a), muls(
 static inline v3 mixv(v3 x, v3 y, v3 a) {
     return mk(x.x * (1.0f - a.x) + y.x * a.x, x.y * (1.0f - a.y) + y.y * a.y, x.z * (1.0f - a.z) + y.z * a.z);
 }
-static inline float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
+static inline float clampf(float x, float lo, float hi) { return rt2pm_fminf(rt2pm_fmaxf(x, lo), hi); }
 static inline float smoothstep(float e0, float e1, float x) {
     float t = clampf((x - e0) / (e1 - e0), 0.0f, 1.0f);
     return t * t * (3.0f - 2.0f * t);
@@ -435,7 +437,7 @@ static v3 trace(const ctx_t* c, v3 origin, v3 dir, uint32_t* rng, uint64_t* segs
                 dir = prevDirection;
             else
                 rayColor = mul(rayColor, attenuation);
-            float p = fmaxf(rayColor.x, fmaxf(rayColor.y, rayColor.z));
+            float p = rt2pm_fmaxf(rayColor.x, rt2pm_fmaxf(rayColor.y, rayColor.z));
             if (rnd(rng) > p) break;
             rayColor = muls(rayColor, 1.0f / p);
         } else {
@@ -448,7 +450,7 @@ static v3 trace(const ctx_t* c, v3 origin, v3 dir, uint32_t* rng, uint64_t* segs
 
 /* normalizeColor, compute.glsl:462-470 */
 static inline v3 normalize_color(v3 c) {
-    float m = fmaxf(fmaxf(c.x, c.y), c.z);
+    float m = rt2pm_fmaxf(rt2pm_fmaxf(c.x, c.y), c.z);
     if (m > 1.0f) return divs(c, m);
     return c;
 }
@@ -734,4 +736,67 @@ float oracle_pinned(int which, float x) {
     case 5: return rt2pm_powf(x, 1.0f / 2.2f);
     default: return 0.0f;
     }
+}
+
+/* One operation of DESIGN.md §Numerics on n rows of operands, by the functions
+ * above — the host twin of the product's numerics_kernel, with its operation
+ * codes.  Rows of 9 input and 4 output words, all binary32 bit patterns. */
+int oracle_numerics(int32_t op, const uint32_t* in9, int64_t n, uint32_t* out4) {
+    if (op < 0 || op > 28 || n < 0 || (n > 0 && (!in9 || !out4))) return -1;
+    for (int64_t i = 0; i < n; i++) {
+        float a[9];
+        for (int k = 0; k < 9; k++) a[k] = rt2pm_u2f(in9[9 * i + k]);
+        v3 u = mk(a[0], a[1], a[2]), v = mk(a[3], a[4], a[5]), q = mk(0.0f, 0.0f, 0.0f);
+        uint32_t state = in9[9 * i], w1 = 0, w3 = 0;
+        float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        int vec = 0, raw1 = 0, raw3 = 0;
+        switch (op) {
+        case 0: r[0] = a[0] / a[1]; break;
+        case 1: r[0] = 1.0f / a[0]; break;
+        case 2: r[0] = sqrtf(a[0]); break;
+        case 3: r[0] = fmaf(a[0], a[1], a[2]); break;
+        case 4: r[0] = a[0] * a[1]; break;
+        case 5: r[0] = a[0] + a[1]; break;
+        case 6: r[0] = a[0] - a[1]; break;
+        case 7: r[0] = rt2pm_fminf(a[0], a[1]); break;
+        case 8: r[0] = rt2pm_fmaxf(a[0], a[1]); break;
+        case 9: r[0] = clampf(a[0], a[1], a[2]); break;
+        case 10: r[0] = dot(u, v); break;
+        case 11: q = cross(u, v), vec = 1; break;
+        case 12: r[0] = length(u); break;
+        case 13: q = normalize(u), vec = 1; break;
+        case 14: q = reflect(u, v), vec = 1; break;
+        case 15: {
+            int refracted;
+            q = refract_(u, v, a[6], &refracted), vec = 1;
+            w3 = refracted ? 1u : 0u, raw3 = 1;
+            break;
+        }
+        case 16: q = mixs(u, v, a[6]), vec = 1; break;
+        case 17: r[0] = smoothstep(a[0], a[1], a[2]); break;
+        case 18: r[0] = rt2pm_expf(a[0]); break;
+        case 19: r[0] = rt2pm_logf(a[0]); break;
+        case 20: r[0] = rt2pm_acosf(a[0]); break;
+        case 21: r[0] = rt2pm_cosf(a[0]); break;
+        case 22: r[0] = rt2pm_sinf(a[0]); break;
+        case 23: r[0] = rt2pm_powf(a[0], a[1]); break;
+        case 24: r[0] = aces1(a[0]); break;
+        case 25: r[0] = srgb1(a[0]); break;
+        case 26: q = sky(u), vec = 1; break;
+        case 27:
+            r[0] = rnd(&state);
+            w1 = state, raw1 = 1;
+            break;
+        case 28:
+            q = rnd_dir(&state), vec = 1;
+            w3 = state, raw3 = 1;
+            break;
+        default: break;
+        }
+        if (vec) r[0] = q.x, r[1] = q.y, r[2] = q.z;
+        for (int k = 0; k < 4; k++) out4[4 * i + k] = rt2pm_f2u(r[k]);
+        if (raw1) out4[4 * i + 1] = w1;
+        if (raw3) out4[4 * i + 3] = w3;
+    }
+    return 0;
 }

@@ -82,6 +82,21 @@ void oracle_sky(const float d[3], float out[3]);
 float oracle_tonemap_srgb(float x);
 float oracle_pinned(int which, float x);
 
+/* One operation of DESIGN.md §Numerics on n rows, by this file's own dot, sky,
+ * aces1 and the rest: in9 = n rows of 9 words, out4 = n rows of 4 words, all
+ * binary32 bit patterns (NaN payloads, zero signs and RNG states kept).
+ * Vectors take words 0-2 and 3-5, a trailing scalar word 6.  op:
+ *    0 a/b   1 1/a   2 sqrt(a)   3 fma(a,b,c)   4 a*b   5 a+b   6 a-b
+ *    7 fminf(a,b)   8 fmaxf(a,b)   9 clampf(x,lo,hi)
+ *   10 dot   11 cross   12 length   13 normalize   14 reflect(I,N)
+ *   15 refract_(I,N,eta): xyz + isRefracted   16 mixs(x,y,a)
+ *   17 smoothstep(e0,e1,x)
+ *   18 exp   19 log   20 acos   21 cos   22 sin   23 pow(a,b)   (rt2pm_*)
+ *   24 aces1   25 srgb1   26 sky(dir)
+ *   27 rnd(state): value, new state   28 rnd_dir(state): xyz + new state
+ * The product's test hook rt2_device_numerics takes the same codes. */
+int oracle_numerics(int32_t op, const uint32_t* in9, int64_t n, uint32_t* out4);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
 //   normalize   = v / sqrt(dot(v,v))      (IEEE / and sqrt)
 //   reflect     = I - (2*dot(N,I)) * N
 //   mix(x,y,a)  = x*(1-a) + y*a
+//   min/max     = rt2pm_fminf / rt2pm_fmaxf (a NaN operand ignored, -0 < +0), clamp = min(max(x,lo),hi)
 //   cos/sin/acos/exp/pow from include/rt2_pinned_math.h
 #pragma once
 
@@ -38,7 +39,7 @@ __device__ __forceinline__ float length(f3 a) { return __builtin_sqrtf(dot(a, a)
 __device__ __forceinline__ f3 normalize(f3 a) { return divs(a, length(a)); }
 __device__ __forceinline__ f3 reflect(f3 i, f3 n) { return sub(i, muls(n, 2.0f * dot(n, i))); }
 __device__ __forceinline__ f3 mixs(f3 x, f3 y, float a) { return add(muls(x, 1.0f - a), muls(y, a)); }
-__device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
+__device__ __forceinline__ float clampf(float x, float lo, float hi) { return rt2pm_fminf(rt2pm_fmaxf(x, lo), hi); }
 __device__ __forceinline__ float smoothstep(float e0, float e1, float x) {
     float t = clampf((x - e0) / (e1 - e0), 0.0f, 1.0f);
     return t * t * (3.0f - 2.0f * t);

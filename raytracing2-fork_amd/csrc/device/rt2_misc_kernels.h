@@ -85,7 +85,7 @@ __device__ __forceinline__ f3 trace_basic(const RenderParams& p, f3 o, f3 d, int
         }
         case RT2_LIGHT: {  // normalizeColor, :462-470
             const f3 e = xyz4(m.emissionColor);
-            const float mx = fmaxf(fmaxf(e.x, e.y), e.z);
+            const float mx = rt2pm_fmaxf(rt2pm_fmaxf(e.x, e.y), e.z);
             return mx > 1.0f ? divs(e, mx) : e;
         }
         case RT2_GLASS: {
@@ -319,7 +319,8 @@ __global__ void resolve_rgb8_kernel(const uint4* acc8, long long n, float frames
 }
 
 // Numerics self-test: the IEEE primitives and pinned functions the path uses,
-// evaluated on the device for comparison with the host (tests/test_gpu_numerics.py).
+// evaluated on the device for comparison with the host (test_device_numerics in
+// tests/test_gpu_parity.py; numerics_kernel below takes a caller's own operands).
 __global__ void selftest_kernel(const float* in, int n, float* out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -335,6 +336,74 @@ __global__ void selftest_kernel(const float* in, int n, float* out) {
     out[10 * i + 7] = rt2pm_sinf(x);
     out[10 * i + 8] = rt2pm_powf(fabsf(y), 1.0f / 2.2f);
     out[10 * i + 9] = 1.0f / x;
+}
+
+// One operation of DESIGN.md §Numerics per launch, on a caller's own operands
+// (tests/test_gpu_numerics.py): row i reads in[9 * i ..] and writes
+// out[4 * i ..], both as binary32 bit patterns, so that NaN payloads, zero
+// signs and RNG states pass through untouched.  Every case calls the function
+// the render and query kernels call (rt2_math.h, rt2_pinned_math.h); vectors
+// take words 0-2 and 3-5, a trailing scalar word 6.  The operation codes are
+// those of oracle_numerics (oracle/rt_oracle.h) and rt2.NUMERICS_OPS.
+__global__ void numerics_kernel(int op, const uint32_t* __restrict__ in, int n, uint32_t* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float a[9];
+    for (int k = 0; k < 9; k++) a[k] = __uint_as_float(in[9 * (size_t)i + k]);
+    const f3 u = mk(a[0], a[1], a[2]), v = mk(a[3], a[4], a[5]);
+    uint32_t state = in[9 * (size_t)i];
+    float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t w1 = 0, w3 = 0;  // words that are no floats: rnd's new state; refract_'s flag, rnd_dir's new state
+    bool raw1 = false, raw3 = false;
+    f3 q = mk(0.0f, 0.0f, 0.0f);
+    bool vec = false;
+    switch (op) {
+    case 0: r[0] = a[0] / a[1]; break;
+    case 1: r[0] = 1.0f / a[0]; break;
+    case 2: r[0] = __builtin_sqrtf(a[0]); break;
+    case 3: r[0] = __builtin_fmaf(a[0], a[1], a[2]); break;
+    case 4: r[0] = a[0] * a[1]; break;
+    case 5: r[0] = a[0] + a[1]; break;
+    case 6: r[0] = a[0] - a[1]; break;
+    case 7: r[0] = rt2pm_fminf(a[0], a[1]); break;
+    case 8: r[0] = rt2pm_fmaxf(a[0], a[1]); break;
+    case 9: r[0] = clampf(a[0], a[1], a[2]); break;
+    case 10: r[0] = dot(u, v); break;
+    case 11: q = cross(u, v), vec = true; break;
+    case 12: r[0] = length(u); break;
+    case 13: q = normalize(u), vec = true; break;
+    case 14: q = reflect(u, v), vec = true; break;
+    case 15: {
+        bool refracted;
+        q = refract_(u, v, a[6], refracted), vec = true;
+        w3 = refracted ? 1u : 0u, raw3 = true;
+        break;
+    }
+    case 16: q = mixs(u, v, a[6]), vec = true; break;
+    case 17: r[0] = smoothstep(a[0], a[1], a[2]); break;
+    case 18: r[0] = rt2pm_expf(a[0]); break;
+    case 19: r[0] = rt2pm_logf(a[0]); break;
+    case 20: r[0] = rt2pm_acosf(a[0]); break;
+    case 21: r[0] = rt2pm_cosf(a[0]); break;
+    case 22: r[0] = rt2pm_sinf(a[0]); break;
+    case 23: r[0] = rt2pm_powf(a[0], a[1]); break;
+    case 24: r[0] = aces1(a[0]); break;
+    case 25: r[0] = srgb1(a[0]); break;
+    case 26: q = sky(u), vec = true; break;
+    case 27:
+        r[0] = rnd(state);
+        w1 = state, raw1 = true;
+        break;
+    case 28:
+        q = rnd_dir(state), vec = true;
+        w3 = state, raw3 = true;
+        break;
+    default: break;
+    }
+    if (vec) r[0] = q.x, r[1] = q.y, r[2] = q.z;
+    for (int k = 0; k < 4; k++) out[4 * (size_t)i + k] = __float_as_uint(r[k]);
+    if (raw1) out[4 * (size_t)i + 1] = w1;
+    if (raw3) out[4 * (size_t)i + 3] = w3;
 }
 
 // Exhaustive check of the reciprocal sequences against IEEE 1.0f / x over a

@@ -441,7 +441,7 @@ __device__ __forceinline__ void shade(Lane& L, const RenderParams& p, float best
             L.d = prevDir;
         else
             L.rayColor = mul(L.rayColor, atten);
-        float pr = fmaxf(L.rayColor.x, fmaxf(L.rayColor.y, L.rayColor.z));
+        float pr = rt2pm_fmaxf(L.rayColor.x, rt2pm_fmaxf(L.rayColor.y, L.rayColor.z));
         if (rnd(L.seed) > pr) {
             end_path<S, LIN>(L, p);
             return;

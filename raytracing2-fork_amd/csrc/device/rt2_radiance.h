@@ -117,7 +117,7 @@ __device__ __forceinline__ void radiance_step(const RenderParams& p, RadLane& L,
             L.d = prevDir;
         else
             L.rayColor = mul(L.rayColor, atten);
-        float pr = fmaxf(L.rayColor.x, fmaxf(L.rayColor.y, L.rayColor.z));
+        float pr = rt2pm_fmaxf(L.rayColor.x, rt2pm_fmaxf(L.rayColor.y, L.rayColor.z));
         if (rnd(L.seed) > pr) {
             L.pk |= RD_DONE;
             return;

@@ -2110,6 +2110,26 @@ extern "C" int rt2_device_selftest(const float* in, int32_t n, float* out10) {
     return 0;
 }
 
+// Not in rt2.h (test hook): one operation of DESIGN.md §Numerics (numerics_kernel's codes) on n rows of 9 input
+// words, giving n rows of 4 output words; host arrays of binary32 bit patterns, one launch.
+extern "C" int rt2_device_numerics(int32_t op, const uint32_t* in9, int32_t n, uint32_t* out4) {
+    if (op < 0 || op > 28 || n < 0 || (n > 0 && (!in9 || !out4))) {
+        rt2h::set_error("rt2_device_numerics: bad argument");
+        return -1;
+    }
+    if (n == 0) return 0;
+    uint32_t *din = nullptr, *dout = nullptr;
+    HIPCHECK(hipMalloc(&din, (size_t)n * 36));
+    HIPCHECK(hipMalloc(&dout, (size_t)n * 16));
+    HIPCHECK(hipMemcpy(din, in9, (size_t)n * 36, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(numerics_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, op, din, n, dout);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(out4, dout, (size_t)n * 16, hipMemcpyDeviceToHost));
+    (void)hipFree(din);
+    (void)hipFree(dout);
+    return 0;
+}
+
 // Not in rt2.h (test hook): copies one of the scene's derived device arrays to
 // host memory: 0 = pre-transformed triangles (3 float4 each), 1 = the filter
 // records in the 16x16x32 layout, 2 = their per-triangle tau, 3 = sweep_k16 records,

@@ -99,7 +99,7 @@ __device__ __forceinline__ void shade_step(const RenderParams& p, ShadeLane& L, 
     }
     case RT2_LIGHT: {  // normalizeColor, :462-470
         const f3 e = xyz4(m.emissionColor);
-        const float mx = fmaxf(fmaxf(e.x, e.y), e.z);
+        const float mx = rt2pm_fmaxf(rt2pm_fmaxf(e.x, e.y), e.z);
         L.cum = mx > 1.0f ? divs(e, mx) : e;
         L.st = SH_DONE;
         return;

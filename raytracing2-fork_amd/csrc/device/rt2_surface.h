@@ -77,7 +77,7 @@ __device__ __forceinline__ SurfaceRec surface_record(const RenderParams& p, cons
     }
     case RT2_LIGHT: {  // normalizeColor, :462-470; returned as it is
         const f3 e = xyz4(m.emissionColor);
-        const float mx = fmaxf(fmaxf(e.x, e.y), e.z);
+        const float mx = rt2pm_fmaxf(rt2pm_fmaxf(e.x, e.y), e.z);
         cum = mx > 1.0f ? divs(e, mx) : e;
         break;
     }

@@ -321,6 +321,7 @@ def lib() -> C.CDLL:
         "rt2_unshard_slabs": (C.c_int, [P, I32, I32, I32, Shard, P, P]),
         "rt2_render_host_gather": (C.c_int, [P, C.POINTER(Uniforms), U32, U32, Shard, P, I32, P, P]),
         "rt2_device_selftest": (C.c_int, [P, I32, P]),
+        "rt2_device_numerics": (C.c_int, [I32, P, I32, P]),
         "rt2_device_rcp_check": (C.c_int, [U32, U32, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(U32)]),
         "rt2_device_div_check": (C.c_int, [U32, C.c_ulonglong, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(U32)]),
         "rt2_variant_name": (C.c_char_p, [C.c_int]),
@@ -1131,6 +1132,28 @@ def device_selftest(x: np.ndarray) -> np.ndarray:
     x = np.ascontiguousarray(x, dtype=np.float32)
     out = np.zeros((len(x), 10), dtype=np.float32)
     _check(lib().rt2_device_selftest(x.ctypes.data, len(x), out.ctypes.data), "device_selftest")
+    return out
+
+
+# rt2_device_numerics (test hook): the operation codes of numerics_kernel, which oracle_numerics shares.  Operands
+# are words of a 9-word row (vectors in words 0-2 and 3-5, a trailing scalar in word 6), results words of a 4-word
+# row (refract_: xyz + its flag; rnd: value, new state; rnd_dir: xyz + new state).
+NUMERICS_OPS = {name: code for code, name in enumerate((
+    "div", "rcp", "sqrt", "fma", "mul", "add", "sub", "fmin", "fmax", "clamp", "dot", "cross", "length",
+    "normalize", "reflect", "refract", "mix", "smoothstep", "exp", "log", "acos", "cos", "sin", "pow", "aces1",
+    "srgb1", "sky", "rnd", "rnd_dir"))}
+
+
+def device_numerics(op, rows: np.ndarray) -> np.ndarray:
+    """One operation of DESIGN.md §Numerics on the device, by the functions the kernels call: rows is (n, 9) uint32
+    bit patterns (fewer columns are padded with zeros), the result (n, 4) uint32; one launch."""
+    code = NUMERICS_OPS[op] if isinstance(op, str) else int(op)
+    rows = np.asarray(rows, dtype=np.uint32)
+    assert rows.ndim == 2 and rows.shape[1] <= 9
+    full = np.zeros((len(rows), 9), np.uint32)
+    full[:, :rows.shape[1]] = rows
+    out = np.zeros((len(rows), 4), np.uint32)
+    _check(lib().rt2_device_numerics(code, full.ctypes.data, len(full), out.ctypes.data), "device_numerics")
     return out
 
 
